@@ -10,7 +10,15 @@ A "step" is SURVEY.md §8(d)'s "prove": `zkp_prove` wall-clock from the host
 trace (a pageable numpy array, built before timing) to the serialized proof
 bytes, PCIe upload included. `value` = proofs/s and `ms_per_step` = mean
 ms/proof of those calls; `step_ms` gives their median and min (BASELINE.md:35).
-Extra keys: `trace_resident` (the same proof by `zkp_prove_device` with the
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what that
+headline needs: it builds the trace, proves W times untimed, times N proofs and
+prints the result line. `--dump-outputs DIR` also writes what the last timed
+proof returned to its caller (the proof bytes and the transcript summary) as
+`DIR/<name>.npy`; the trace is seeded, so two builds can be compared output for
+output. Everything below runs only with `--full`, which adds its keys to the line.
+
+Extra keys (`--full`): `trace_resident` (the same proof by `zkp_prove_device` with the
 trace already in HBM; never `value`), `first_proof_ms` (first proof of a
 fresh context: domain tables built cold), `sustained` (proofs/s over a few
 seconds), `c3` (BASELINE configs[2]: the aggregation AIR, 64 updates, 2^18 x
@@ -290,6 +298,12 @@ def parse():
     ap.add_argument("--log-n", type=int, default=None, help="trace length 2^k (default: the config's)")
     ap.add_argument("--mode", choices=["replicas", "sharded"], default="replicas")
     ap.add_argument("--blowup", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every other leg (per-kernel table and roofline, trace-resident, "
+                         "sustained, session, concurrent, C1, C3, reference flow, rank emulation, CPU baseline and "
+                         "oracle checks, the sharded leg at N > 1); the options below select among those legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed proof returned (proof bytes, transcript) as DIR/<name>.npy")
     ap.add_argument("--sustain-s", type=float, default=3.0, help="seconds of back-to-back proofs for `sustained`")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true")
@@ -309,7 +323,10 @@ def parse():
                     help="skip the tampered-trace proofs (keeps PMC passes to valid proofs)")
     ap.add_argument("--air", choices=["mimc", "agg"], default="mimc",
                     help="mimc = C2 (default, the BASELINE metric); agg = C3 GlobalUpdate (64 updates, 2^18 rows)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full and (args.stats or args.sharded_leg):
+        ap.error("--stats and --sharded-leg report legs that run only with --full")
+    return args
 
 
 def make_workload(air: str, sharded: bool, log_n, blowup: int, seed_rank: int, ctx):
@@ -631,6 +648,45 @@ def measure(ctx, headline, steps: int, warmup: int, dist=None, sync=None, device
     ctx.set_profiling(False)
     return {"first_ms": first_ms, "kernels": kernels, "dom_name": dom_name, "elapsed": elapsed, "times": times,
             "proof": proof, "tr": tr, "stats": ctx.stats_table()}
+
+
+def measure_plain(headline, steps: int, warmup: int, dist=None, sync=None, device=None) -> dict:
+    """The headline's timing alone: `warmup` untimed proofs (the first builds the domain
+    tables), then `steps` timed proofs with no launch bracketed by events."""
+    from zk_stark_project_amd.replicas import timed_replicas
+    times = []
+    elapsed, _, (proof, tr) = timed_replicas(headline, steps, warmup, dist=dist, device_sync=sync, device=device,
+                                              times=times)
+    return {"elapsed": elapsed, "times": times, "proof": proof, "tr": tr}
+
+
+def dump_outputs(dirname: str, proof: bytes, tr, rank: int = 0) -> dict:
+    """What the last timed proof gave its caller, as `dirname/<name>.npy` (rank r > 0 of a
+    replicas run: `<name>_rank<r>.npy`): the serialized proof and the transcript fields
+    (roots, z, grinding nonce as little-endian bytes; one float32 per byte, exact) and the
+    query positions (float64, exact below 2^53). Returns name -> shape."""
+    import numpy as np
+
+    def u8(b) -> "np.ndarray":
+        return np.frombuffer(bytes(b), dtype=np.uint8).astype(np.float32)
+    layers = int(tr.num_fri_layers)
+    z = int(tr.z.lo) | (int(tr.z.hi) << 64)
+    arrays = {
+        "proof": u8(proof),
+        "trace_root": u8(tr.trace_root),
+        "constraint_root": u8(tr.constraint_root),
+        "fri_roots": u8(b"".join(bytes(tr.fri_roots[i]) for i in range(layers))).reshape(layers, 32),
+        "remainder_commitment": u8(tr.remainder_commitment),
+        "pow_nonce": u8(int(tr.pow_nonce).to_bytes(8, "little")),
+        "z": u8(z.to_bytes(16, "little")),
+        "query_positions": np.array([int(tr.query_positions[i]) for i in range(tr.num_unique_queries)],
+                                    dtype=np.float64),
+    }
+    os.makedirs(dirname, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def step_summary(times) -> dict:
@@ -1014,8 +1070,10 @@ def main():
     air_id, width, n, opts, trace = wl["air_id"], wl["width"], wl["n"], wl["opts"], wl["trace"]
     pub = wl["prover"].get_pub_inputs(trace).to_elements()
     host_trace = trace.data  # (width, n, 2) uint64, pageable host memory
-    d_trace = ctx.alloc(host_trace.nbytes)
-    ctx.to_device(d_trace, host_trace)
+    d_trace = None
+    if args.full:  # the trace-resident leg's copy of the trace in HBM
+        d_trace = ctx.alloc(host_trace.nbytes)
+        ctx.to_device(d_trace, host_trace)
 
     comm = None
     if sharded:
@@ -1049,8 +1107,56 @@ def main():
     # then the sharded proof); the trace-resident proof is reported beside it
     headline, second = prove_once, prove_dev
     sync = cuda_sync if dist is not None else None
-    m = measure(ctx, headline, args.steps, args.warmup, dist=dist, sync=sync, device=f"cuda:{local_rank}")
-    elapsed, proof, tr, kernels, dom_name = m["elapsed"], m["proof"], m["tr"], m["kernels"], m["dom_name"]
+    if args.full:
+        m = measure(ctx, headline, args.steps, args.warmup, dist=dist, sync=sync, device=f"cuda:{local_rank}")
+    else:
+        m = measure_plain(headline, args.steps, args.warmup, dist=dist, sync=sync, device=f"cuda:{local_rank}")
+    elapsed, proof, tr = m["elapsed"], m["proof"], m["tr"]
+    ms = elapsed / args.steps * 1e3
+    dumped = None
+    if args.dump_outputs and (rank == 0 or not sharded):  # every rank of a sharded proof holds the same bytes
+        dumped = dump_outputs(args.dump_outputs, proof, tr, rank)
+
+    metric = (f"STARK proofs/sec + prove-time ms, MiMC AIR 2^{wl['log_n']}-step trace" if args.air == "mimc"
+              else f"STARK proofs/sec + prove-time ms, aggregation AIR 2^{wl['log_n']}-step trace")
+    if sharded:
+        metric += ", one proof domain-sharded over all GPUs"
+    head = {
+        "metric": metric,
+        "value": round(aggregate_rate(1 if sharded else world, args.steps, elapsed), 3),
+        "unit": "proofs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms, 3),
+        "higher_is_better": True,
+        "scaling": "strong" if sharded else "weak",
+        "vs_baseline": None,
+        "dtype": "f128 (u128 mod 2^128-45*2^40+1)",
+        "data": "synthetic (MiMC trace x0=42e6+rank)" if args.air == "mimc" else "synthetic (seeded u64 model entries)",
+        "config": {"workload": wl["workload"],
+                   "trace_length": n, "trace_width": width, "blowup": opts.blowup_factor, "num_queries": 40,
+                   "grinding": 21, "fri_folding": 16, "fri_remainder_max_degree": 7,
+                   "parallelism": f"coset-sharded{world} (RCCL)" if sharded else f"replicas{world}",
+                   "env": zkp_env(),
+                   "step": ("GlobalUpdate trace built on each rank's device from the updates + zkp_prove_sharded"
+                            if sharded and args.air == "agg" else
+                            "zkp_prove_sharded from the host trace: each rank uploads its row slice" if sharded else
+                            "zkp_prove: host trace (pageable numpy) -> proof bytes, PCIe upload included "
+                            "(SURVEY.md §8(d) 'prove')")},
+        "step_ms": step_summary(m["times"]),
+    }
+    if dumped is not None:
+        head["dumped_outputs"] = dumped
+    if not args.full:
+        if comm is not None:
+            comm.close()
+        if rank == 0:
+            print(json.dumps({**head, "proof_bytes": len(proof)}), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    kernels, dom_name = m["kernels"], m["dom_name"]
     # the same proof with the trace already in HBM (zkp_prove_device / a device-resident
     # sharded proof): reported beside the headline, never as `value`
     el_in, _, _ = timed_replicas(second, args.steps, 1, dist=dist, device_sync=sync, device=f"cuda:{local_rank}")
@@ -1107,7 +1213,6 @@ def main():
     R = world if sharded else 1
     B = opts.blowup_factor
     host_stages = {k: v for k, v in m["stats"].items() if k.startswith("host_")}
-    ms = elapsed / args.steps * 1e3
     roofline = roofline_of(m, wl, R, args.steps, ms, args.air, args.mode)
 
     cpu = None
@@ -1143,34 +1248,8 @@ def main():
                       f"proof bytes identical to GPU: {same}",
         }
 
-    metric = (f"STARK proofs/sec + prove-time ms, MiMC AIR 2^{wl['log_n']}-step trace" if args.air == "mimc"
-              else f"STARK proofs/sec + prove-time ms, aggregation AIR 2^{wl['log_n']}-step trace")
-    if sharded:
-        metric += ", one proof domain-sharded over all GPUs"
     out = {
-        "metric": metric,
-        "value": round(aggregate_rate(1 if sharded else world, args.steps, elapsed), 3),
-        "unit": "proofs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms, 3),
-        "higher_is_better": True,
-        "scaling": "strong" if sharded else "weak",
-        "vs_baseline": None,
-        "dtype": "f128 (u128 mod 2^128-45*2^40+1)",
-        "data": "synthetic (MiMC trace x0=42e6+rank)" if args.air == "mimc" else "synthetic (seeded u64 model entries)",
-        "config": {"workload": wl["workload"],
-                   "trace_length": n, "trace_width": width, "blowup": B, "num_queries": 40, "grinding": 21,
-                   "fri_folding": 16, "fri_remainder_max_degree": 7,
-                   "parallelism": f"coset-sharded{world} (RCCL)" if sharded else f"replicas{world}",
-                   "env": zkp_env(),
-                   "step": ("GlobalUpdate trace built on each rank's device from the updates + zkp_prove_sharded"
-                            if sharded and args.air == "agg" else
-                            "zkp_prove_sharded from the host trace: each rank uploads its row slice" if sharded else
-                            "zkp_prove: host trace (pageable numpy) -> proof bytes, PCIe upload included "
-                            "(SURVEY.md §8(d) 'prove')")},
-        "step_ms": step_summary(m["times"]),
+        **head,
         "trace_resident": {
             "ms_per_proof": round(el_in / args.steps * 1e3, 3),
             "proofs_per_s": round(aggregate_rate(1 if sharded else world, args.steps, el_in), 3),

@@ -6,7 +6,7 @@ set -o pipefail
 A=$1; B=$2
 for r in 1 2; do
   for L in "$A" "$B"; do
-    out=$(ZKP_LIB=$L timeout -k 10 240 python bench.py --no-cpu-baseline --no-verify --sustain-s 0 --no-concurrent \
+    out=$(ZKP_LIB=$L timeout -k 10 240 python bench.py --full --no-cpu-baseline --no-verify --sustain-s 0 --no-concurrent \
           --no-c3 --no-rank-emulation --no-tampered --steps 20) || exit 1
     echo "$L $(echo "$out" | python -c '
 import json,sys

@@ -4,7 +4,7 @@ set -u
 export TMPDIR=/tmp
 A=$1; B=$2; TAG=$3; shift 3
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
-ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-verify --sustain-s 0 $*"
+ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline --no-verify --sustain-s 0 $*"
 i=0
 for L in "$A" "$B"; do
   OUT=$ROOT/gpurun_out/abv_${TAG}_$i

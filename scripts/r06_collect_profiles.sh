@@ -10,10 +10,11 @@ for pair in "r06_c2:mimc_c2" "r06_c3:agg_c3"; do
   cp $d/sq.txt profiles/r06_pmc_sq_$wl.txt
   cp $d/trace/run_kernel_stats.csv profiles/r06_rocprof_kernel_stats_$wl.csv
 done
-if [ -f gpurun_out/prof_judged/run_kernel_stats.csv ]; then
-  cp gpurun_out/prof_judged/run_kernel_stats.csv profiles/r06_rocprof_kernel_stats_judged.csv
-  python3 scripts/judged_kernel_summary.py gpurun_out/prof_judged/run_kernel_trace.csv gpurun_out/prof_judged.json \
+OUT=${OUT:-bench_out}  # where scripts/r06_profiles.sh put the judged run
+if [ -f $OUT/prof_judged/run_kernel_stats.csv ]; then
+  cp $OUT/prof_judged/run_kernel_stats.csv profiles/r06_rocprof_kernel_stats_judged.csv
+  python3 scripts/judged_kernel_summary.py $OUT/prof_judged/run_kernel_trace.csv $OUT/prof_judged.json \
     > profiles/r06_judged_kernel_summary.json
-  tail -1 gpurun_out/prof_judged.json > profiles/r06_bench_under_rocprof.json
+  tail -1 $OUT/prof_judged.json > profiles/r06_bench_under_rocprof.json
 fi
 echo collected
