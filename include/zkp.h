@@ -335,6 +335,28 @@ int zkp_build_global_update_trace(zkp_ctx* ctx, const zkp_felt* raw_global, cons
                                   const zkp_felt* local_updates, uint64_t ndev, zkp_felt k, uint64_t n,
                                   void* d_trace_out, zkp_felt* final_state /* nullable */);
 
+/* TrainingUpdateProver::build_trace on the device (src/training/prover.rs:90-218):
+ * writes the 240 x n column-major trace into HBM at d_trace_out (ready for
+ * zkp_prove_device). initial_state = the 120 felts of row 0 before masking:
+ * [value, sign] pairs, w row-major (6 x 9) then b (6) (prover.rs:98-103); x_batch,
+ * x_sign = bs x 9 features and their signs, y_batch = bs x 6 one-hot labels
+ * (row-major; unused when bs = 0). The bs signed fixed-point SGD steps
+ * (src/signed.rs, src/helper.rs:245-400) run on the device; signs are field
+ * elements and any canonical value is taken as the reference's arithmetic takes it.
+ * masks = n x 120 u64 in host memory, row t's 120 masks contiguous. Rows: column
+ * c < 120 of row t = state_min(t, bs)[c] + masks[t][c], column 120 + c = masks[t][c].
+ * n must be a power of two >= 16 and > bs (ZKP_ERR_TRACE_SHAPE otherwise); a felt
+ * >= p is ZKP_ERR_ARGUMENT; a learning_rate or precision of 0 is accepted
+ * (winterfell inv(0) = 0). first_last (nullable, 240 felts) receives columns 0..119
+ * of row 0, then of row n - 1: the `initial_masked` and `final_masked` of
+ * TrainingUpdateProver::get_pub_inputs (prover.rs:236-270). raw_states (nullable,
+ * (bs + 1) x 120 felts) receives the unmasked state after each sample. */
+int zkp_build_training_update_trace(zkp_ctx* ctx, const zkp_felt* initial_state, const zkp_felt* x_batch,
+                                    const zkp_felt* x_sign, const zkp_felt* y_batch, uint64_t bs,
+                                    zkp_felt learning_rate, zkp_felt precision, const uint64_t* masks, uint64_t n,
+                                    void* d_trace_out, zkp_felt* first_last /* nullable */,
+                                    zkp_felt* raw_states /* nullable */);
+
 /* ---- profiling ------------------------------------------------------- */
 /* When enabled, every kernel launch is bracketed with HIP events on the
  * stream it runs on; zkp_kernel_stats reports per-kernel launch count and

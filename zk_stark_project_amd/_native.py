@@ -75,6 +75,7 @@ EXPORTED = [
     "zkp_comm_rccl_create", "zkp_comm_destroy", "zkp_comm_rank", "zkp_comm_world", "zkp_comm_backend_world", "zkp_comm_check",
     "zkp_prove_sharded_device",
     "zkp_verify", "zkp_build_global_update_trace", "zkp_set_profiling_kernel",
+    "zkp_build_training_update_trace",
     "zkp_session_create", "zkp_session_destroy", "zkp_session_trace_lde", "zkp_eval_constraints",
     "zkp_composition_commit", "zkp_ood_frame", "zkp_deep_fri", "zkp_query", "zkp_comm_host_create",
     "zkp_session_shape",
@@ -173,6 +174,7 @@ def load():
         L.zkp_verify.argtypes = [i32, ctypes.c_char_p, u64, vp, u64, popt]
         L.zkp_verify.restype = i32
         L.zkp_build_global_update_trace.argtypes = [vp, vp, vp, vp, u64, Felt, u64, vp, vp]
+        L.zkp_build_training_update_trace.argtypes = [vp, vp, vp, vp, vp, u64, Felt, Felt, vp, u64, vp, vp, vp]
         L.zkp_comm_host_create.argtypes = [i32, i32, ctypes.POINTER(HostTransport), ctypes.POINTER(vp)]
         L.zkp_session_create.argtypes = [vp, i32, u32, u64, vp, u64, popt, ctypes.POINTER(vp)]
         L.zkp_session_destroy.argtypes = [vp]
@@ -432,6 +434,36 @@ class Context:
                                                     len(local), kf, n, d_out, final.ctypes.data)
         self._check(rc, "zkp_build_global_update_trace")
         return [int(lo) | (int(hi) << 64) for lo, hi in final]
+
+    def build_training_update_trace(self, initial_state, x_batch, x_sign, y_batch, learning_rate: int,
+                                    precision: int, masks: np.ndarray, n: int, d_out: int,
+                                    want_raw_states: bool = False):
+        """zkp_build_training_update_trace: TrainingUpdate trace (240 x n) into HBM at d_out.
+        initial_state: 120 ints ([v, s] pairs, w row-major then b); x_batch, x_sign: bs x 9,
+        y_batch: bs x 6; masks: (n, 120) uint64, passed as it is. Returns (first, last), the
+        masked halves (120 ints each) of rows 0 and n - 1, and with want_raw_states also
+        the (bs + 1) x 120 unmasked states."""
+        bs = len(x_batch)
+        flat = lambda rows: _felts([v for row in rows for v in row]) if bs else None
+        st, x, xs, y = _felts(initial_state), flat(x_batch), flat(x_sign), flat(y_batch)
+        masks = np.ascontiguousarray(masks, dtype=np.uint64)
+        if st.shape != (120, 2) or masks.shape != (n, 120):
+            raise ValueError("initial_state must hold 120 felts and masks (n, 120) uint64")
+        if bs and (x.shape, xs.shape, y.shape) != ((bs * 9, 2), (bs * 9, 2), (bs * 6, 2)):
+            raise ValueError("x_batch, x_sign must be bs x 9 and y_batch bs x 6")
+        fl = np.zeros((240, 2), dtype=np.uint64)
+        raw = np.zeros(((bs + 1) * 120, 2), dtype=np.uint64) if want_raw_states else None
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        mask64 = 2**64 - 1
+        rc = self.lib.zkp_build_training_update_trace(
+            self.ptr, ptr(st), ptr(x), ptr(xs), ptr(y), bs, Felt(learning_rate & mask64, learning_rate >> 64),
+            Felt(precision & mask64, precision >> 64), masks.ctypes.data, n, d_out, fl.ctypes.data, ptr(raw))
+        self._check(rc, "zkp_build_training_update_trace")
+        fl = _ints(fl)
+        if want_raw_states:
+            raw = _ints(raw)
+            return fl[:120], fl[120:], [raw[i * 120:(i + 1) * 120] for i in range(bs + 1)]
+        return fl[:120], fl[120:]
 
     def trace_lde_commit(self, trace: np.ndarray, blowup: int, want_lde: bool = True):
         trace = np.ascontiguousarray(trace, dtype=np.uint64)

@@ -2,7 +2,8 @@
 
 The reference binary's CLI (/root/reference/src/main.rs:55-74, flow :79-493)
 driven by the MI355X prover: per-device TrainingUpdate proofs, then the
-GlobalUpdate aggregation proof, each verified like the reference does. The
+GlobalUpdate aggregation proof, each verified like the reference does (the
+setup and proof steps build the training traces on the device). The
 stdout lines the reference prints are kept verbatim because the Python
 harness parses them (/root/reference/verification/time_memory_analytics/
 analyze.py:416-506, regexes :476-482): "Training proof size: N bytes",
@@ -111,9 +112,9 @@ def main(argv=None) -> int:
     print(f"DEBUG: Step = {args.step.capitalize()}")
 
     from . import _native
-    from .air import GlobalUpdateAir, TrainingUpdateAir
+    from .air import TU_STATE, GlobalUpdateAir, TrainingUpdateAir
     from .options import ProofOptions
-    from .prover import verify
+    from .prover import Proof, verify
 
     opts = ProofOptions.reference()  # main.rs:98-107
     rng = random.Random(args.seed)
@@ -131,6 +132,7 @@ def main(argv=None) -> int:
     ctx = _native.Context(args.device) if args.step != "witness" else None
     step_start = time.perf_counter()
     client_reps, total_training = [], 0
+    d_trace = None  # the training traces' device allocation (one shape: reused by every device)
 
     if args.step in ("setup", "proof") and args.verbose and args.step == "setup":
         print("--- Client Training Updates ---")
@@ -150,20 +152,27 @@ def main(argv=None) -> int:
         print(f"DEBUG: {'Device' if args.step == 'setup' else 'Proof step - Device'} {i + 1}, "
               f"batch size {args.bs}")
         t0 = time.perf_counter()
-        trace = tp.build_trace()
-        print(f"DEBUG: Trace dimensions - length: {trace.length()}, width: {trace.width()}")
-        proof = tp.prove(trace)
+        # the trace is built in HBM (SGD chain and masked rows on the device) and proved there
+        width, length = 2 * TU_STATE, tp.trace_length
+        if d_trace is None:
+            d_trace = ctx.alloc(width * length * 16)
+        tp.build_trace_device(ctx, d_trace)
+        print(f"DEBUG: Trace dimensions - length: {length}, width: {width}")
+        pub = tp.get_pub_inputs()
+        proof = Proof(*ctx.prove_device(TrainingUpdateAir.AIR_ID, d_trace, width, length, pub.to_elements(), opts))
         size = len(proof.to_bytes())
         total_training += size
         if args.verbose and args.step == "setup":
             print(f"Device {i + 1:>2}: ZK proof for {args.bs} samples: gen = {_ms(t0):>4}ms, size = {size} bytes")
             print(f"Training proof size: {size} bytes")
         try:
-            verify(TrainingUpdateAir, proof, tp.get_pub_inputs(trace), opts)
+            verify(TrainingUpdateAir, proof, pub, opts)
         except _native.VerifierError as e:
             print(f"training proof failed!: {e}", file=sys.stderr)
             return 101
-        client_reps.append(trace.get(0, trace.length() - 1))
+        client_reps.append(pub.final_masked[0])
+    if d_trace is not None:
+        ctx.free(d_trace)
 
     if args.step == "setup":
         t0 = time.perf_counter()

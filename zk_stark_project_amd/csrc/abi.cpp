@@ -22,6 +22,9 @@ bool device_is_gfx950(int device) {
   known[device] = ok;
   return ok;
 }
+
+// a TrainingUpdate state: 60 cells of a (value, sign) pair, half the trace's width
+constexpr uint32_t TU_STATE = TU_W / 2;
 }  // namespace
 
 extern "C" {
@@ -248,6 +251,53 @@ int zkp_build_global_update_trace(zkp_ctx* ctx, const zkp_felt* raw_global, cons
                                  hipMemcpyDeviceToHost, ctx->stream));
     ctx->sync();
     ctx->collect_prof();
+    return 0;
+  });
+}
+
+int zkp_build_training_update_trace(zkp_ctx* ctx, const zkp_felt* initial_state, const zkp_felt* x_batch,
+                                    const zkp_felt* x_sign, const zkp_felt* y_batch, uint64_t bs,
+                                    zkp_felt learning_rate, zkp_felt precision, const uint64_t* masks, uint64_t n,
+                                    void* d_trace_out, zkp_felt* first_last, zkp_felt* raw_states) {
+  return guarded(ctx, [&] {
+    HIP_CHECK(hipSetDevice(ctx->device));
+    if (!initial_state || !masks || !d_trace_out || (bs && (!x_batch || !x_sign || !y_batch)))
+      return (int)ZKP_ERR_ARGUMENT;
+    if (n < 16 || (n & (n - 1)) || n <= bs || n > (1ull << MAX_LOG_TRACE)) return (int)ZKP_ERR_TRACE_SHAPE;
+    const felt lr = make(learning_rate.lo, learning_rate.hi), pr = make(precision.lo, precision.hi);
+    auto canon = [](const zkp_felt* v, uint64_t cnt) {
+      for (uint64_t i = 0; i < cnt; i++)
+        if (ge_p(make(v[i].lo, v[i].hi))) return false;
+      return true;
+    };
+    if (ge_p(lr) || ge_p(pr) || !canon(initial_state, TU_STATE) || !canon(x_batch, bs * TU_FE) ||
+        !canon(x_sign, bs * TU_FE) || !canon(y_batch, bs * TU_AC))
+      return (int)ZKP_ERR_ARGUMENT;
+    // the unmasked states: row 0 uploaded, rows 1..bs by the chain kernel (none for bs = 0)
+    felt* ds = ctx->buf<felt>("tu_states", (bs + 1) * TU_STATE);
+    ctx->upload(ds, initial_state, TU_STATE * 16);
+    if (bs) {
+      std::vector<zkp_felt> in;  // [x | x_sign | y]
+      in.reserve(bs * (2 * TU_FE + TU_AC));
+      in.insert(in.end(), x_batch, x_batch + bs * TU_FE);
+      in.insert(in.end(), x_sign, x_sign + bs * TU_FE);
+      in.insert(in.end(), y_batch, y_batch + bs * TU_AC);
+      felt* din = ctx->buf<felt>("tu_batch", in.size());
+      ctx->upload(din, in.data(), in.size() * 16);
+      // divisors of signed.rs div_generic (0 is accepted: winterfell inv(0) = 0); mse_prime
+      // divides by f64_to_felt(6.0) (helper.rs:245-269)
+      launch_tu_states(ctx->prof, ctx->stream, ds, din, din + bs * TU_FE, din + 2 * bs * TU_FE, (uint32_t)bs,
+                       inv(pr), inv(lr), inv(felt_u64(TU_AC * 1000000ull)));
+    }
+    uint64_t* dm = ctx->buf<uint64_t>("tu_masks", n * TU_STATE);
+    ctx->upload(dm, masks, n * TU_STATE * 8);
+    felt* dfl = ctx->buf<felt>("tu_first_last", 2 * TU_STATE);
+    launch_tu_write(ctx->prof, ctx->stream, dm, ds, bs, n, (felt*)d_trace_out, dfl);
+    if (first_last) ctx->download(first_last, dfl, 2 * TU_STATE * 16);
+    if (raw_states) ctx->download(raw_states, ds, (bs + 1) * TU_STATE * 16);
+    ctx->sync();
+    ctx->collect_prof();
+    ctx->free_retired();  // buffers a larger batch or trace outgrew (no proof's finish follows)
     return 0;
   });
 }

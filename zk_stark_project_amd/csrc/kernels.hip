@@ -1,6 +1,6 @@
 // kernels.hip — CDNA4 (gfx950) kernels of the STARK prover hot path: domain
 // tables, constraint evaluation, composition DFT, OOD, DEEP, gathers and the
-// aggregation trace builder (BLAKE3 / Merkle / transcript / FRI: merkle.hip).
+// aggregation and training trace builders (BLAKE3 / Merkle / transcript / FRI: merkle.hip).
 //
 // All arithmetic is exact f128 integer arithmetic, so results are
 // order-independent and bit-identical to the CPU restatement in oracle/.
@@ -904,6 +904,155 @@ __global__ __launch_bounds__(TPB) void k_gu_tile_write(const felt* __restrict__ 
   }
 }
 
+// --------------------------------------------------- training trace builder
+// TrainingUpdateProver::build_trace on the device (src/training/prover.rs:90-218):
+// the unmasked state after each of the bs samples (k_tu_states: the signed
+// fixed-point SGD step of src/signed.rs and src/helper.rs:245-400, serial over the
+// samples), then row t = [raw_min(t, bs) + mask_t | mask_t] (k_tu_write). A state is
+// 60 cells (w row-major 6 x 9, then b) of a (value, sign) pair: 120 felts.
+constexpr uint32_t TU_AC = 6, TU_FE = 9, TU_WC = TU_AC * TU_FE, TU_CELLS = TU_WC + TU_AC, TU_HALF = 2 * TU_CELLS;
+
+// a signed.rs value: the sign is a felt, combined by field expressions only (any
+// canonical value is a valid sign to the reference's arithmetic, not just 0 and 1)
+struct sfelt {
+  felt v, s;
+};
+
+// s * a + (1 - s) * b for any s, as b + s * (a - b): one product
+__device__ __forceinline__ felt tu_blend(felt s, felt a, felt b) { return add(b, mul(s, sub(a, b))); }
+// Felt::new(u128::MAX) + 1 - v (signed.rs:3: 2^128 mod p is fp::C)
+__device__ __forceinline__ felt tu_wrap(felt v) { return sub(make(fp::C, 0), v); }
+// signed.rs:11-14
+__device__ __forceinline__ felt tu_cleanse(sfelt a) { return tu_blend(a.s, tu_wrap(a.v), a.v); }
+// signed.rs:16-25; a_c, b_c = the operands' cleansed values (kept where they are used twice)
+__device__ __forceinline__ sfelt tu_add(sfelt a, felt a_c, sfelt b, felt b_c) {
+  const felt ind = mul(a.s, b.s);
+  return {tu_blend(ind, sub(tu_wrap(a_c), b_c), add(a.v, b.v)), ind};
+}
+// signed.rs:27-30: a + (-b) with the reference's sign handling (sub(a, 0, b, 0) = a + b)
+__device__ __forceinline__ sfelt tu_sub(sfelt a, felt a_c, sfelt b) {
+  const sfelt nb{b.v, sub(one(), b.s)};
+  return tu_add(a, a_c, nb, tu_cleanse(nb));
+}
+// signed.rs:32-39 from the cleansed operands and their signs
+__device__ __forceinline__ sfelt tu_mul(felt a_c, felt sa, felt b_c, felt sb) {
+  const felt q = mul(a_c, b_c), ab = mul(sa, sb);
+  const felt sign = sub(add(sa, sb), add(ab, ab));
+  return {tu_blend(sign, tu_wrap(q), q), sign};
+}
+// signed.rs:32-48 by a factor of sign 0 (a constant, or the inverse of a divisor): its
+// cleansed value is itself and the result's sign s_a + 0 - 2 * s_a * 0 is s_a
+__device__ __forceinline__ sfelt tu_scale(sfelt a, felt k) {
+  const felt q = mul(tu_cleanse(a), k);
+  return {tu_blend(a.s, tu_wrap(q), q), a.s};
+}
+
+// states[0] = the initial state; states[k + 1] = the state after sample k. One wave:
+// thread c < 60 owns cell c. x, xs: bs x 9, y: bs x 6; pr_inv, lr_inv, ac_inv = the
+// inverses of the precision, the learning rate and f64_to_felt(6.0). The steps are
+// serial and one wave's field products run one after the other, so a step's time is
+// its chain of products: cleansed values are kept beside the values they belong to,
+// and the next sample's features are fetched by threads that idle during the fold.
+__global__ __launch_bounds__(64) void k_tu_states(felt* __restrict__ states, const felt* __restrict__ x,
+                                                  const felt* __restrict__ xs, const felt* __restrict__ y,
+                                                  uint32_t bs, felt pr_inv, felt lr_inv, felt ac_inv) {
+  // state (value, sign, cleansed), forward products, errors, features (two samples)
+  __shared__ felt sv[TU_CELLS], ss[TU_CELLS], sc[TU_CELLS], pv[TU_WC], ps[TU_WC], pc[TU_WC], ev[TU_AC], es[TU_AC],
+      xsg[2][TU_FE], xc[2][TU_FE];
+  const uint32_t c = threadIdx.x;
+  const bool cell = c < TU_CELLS, wcell = c < TU_WC;
+  const uint32_t i = wcell ? c / TU_FE : c - TU_WC, j = c % TU_FE;  // w[i][j] or b[i]
+  const bool feeder = c >= TU_AC && c < TU_AC + TU_FE;              // fetches feature c - TU_AC
+  auto fetch = [&](uint32_t k) {
+    const sfelt f{x[k * TU_FE + c - TU_AC], xs[k * TU_FE + c - TU_AC]};
+    xsg[k & 1][c - TU_AC] = f.s;
+    xc[k & 1][c - TU_AC] = tu_cleanse(f);
+  };
+  if (cell) {
+    const sfelt own{states[2 * c], states[2 * c + 1]};
+    sv[c] = own.v;
+    ss[c] = own.s;
+    sc[c] = tu_cleanse(own);
+  }
+  if (feeder && bs) fetch(0);
+  for (uint32_t k = 0; k < bs; k++) {
+    const felt* fs = xsg[k & 1];
+    const felt* fc = xc[k & 1];
+    __syncthreads();
+    // forward (helper.rs:282-330): the 54 products in parallel, then per output a
+    // serial fold in the reference's order (signed add is not associative)
+    if (wcell) {
+      const sfelt p = tu_mul(sc[c], ss[c], fc[j], fs[j]);
+      pv[c] = p.v;
+      ps[c] = p.s;
+      pc[c] = tu_cleanse(p);
+    }
+    __syncthreads();
+    if (c < TU_AC) {
+      sfelt t{zero(), zero()};
+#pragma unroll 1
+      for (uint32_t f = c * TU_FE; f < (c + 1) * TU_FE; f++) t = tu_add(t, tu_cleanse(t), {pv[f], ps[f]}, pc[f]);
+      const sfelt wx = tu_scale(t, pr_inv);
+      const sfelt out = tu_add(wx, tu_cleanse(wx), {sv[TU_WC + c], ss[TU_WC + c]}, sc[TU_WC + c]);
+      // mse_prime (helper.rs:245-269): subtract(pred, true, sign, 0) adds
+      const sfelt d = tu_sub(out, tu_cleanse(out), {y[k * TU_AC + c], zero()});
+      const sfelt e = tu_scale(tu_scale(d, from_u64(2000000)), ac_inv);
+      ev[c] = e.v;
+      es[c] = e.s;
+    } else if (feeder && k + 1 < bs) {
+      fetch(k + 1);
+    }
+    __syncthreads();
+    // backward (helper.rs:345-400): every cell from its own old value, err[i] and x[j]
+    sfelt nw{zero(), zero()};
+    if (cell) {
+      const sfelt err{ev[i], es[i]};
+      const sfelt g = wcell ? tu_scale(tu_scale(tu_mul(tu_cleanse(err), err.s, fc[j], fs[j]), lr_inv), pr_inv)
+                            : tu_scale(err, lr_inv);
+      nw = tu_sub({sv[c], ss[c]}, sc[c], g);
+      felt* row = states + (uint64_t)(k + 1) * TU_HALF;
+      row[2 * c] = nw.v;
+      row[2 * c + 1] = nw.s;
+    }
+    __syncthreads();  // the old state is read by every thread before it changes
+    if (cell) {
+      sv[c] = nw.v;
+      ss[c] = nw.s;
+      sc[c] = tu_cleanse(nw);
+    }
+  }
+}
+
+// Row-major u64 masks -> 240 column-major felt columns: a tile of TU_ROWS rows x 120
+// masks goes through LDS, read from HBM as one contiguous run and written as runs of
+// TU_ROWS consecutive rows per column. The odd pitch (121 x 8 B) puts the TU_ROWS rows
+// of a column in distinct LDS banks. The tile is 30976 B. first_last = the masked
+// columns of row 0, then of row n - 1.
+constexpr uint32_t TU_ROWS = 32, TU_PITCH = TU_HALF + 1;
+
+__global__ __launch_bounds__(TPB) void k_tu_write(const uint64_t* __restrict__ masks,
+                                                  const felt* __restrict__ states, uint64_t bs, uint64_t n,
+                                                  felt* __restrict__ out, felt* __restrict__ first_last) {
+  __shared__ uint64_t tile[TU_ROWS * TU_PITCH];
+  const uint64_t t0 = (uint64_t)blockIdx.x * TU_ROWS;
+  const uint32_t rows = n - t0 < TU_ROWS ? (uint32_t)(n - t0) : TU_ROWS;
+  const uint64_t* src = masks + t0 * TU_HALF;
+  for (uint32_t e = threadIdx.x; e < rows * TU_HALF; e += TPB) tile[e / TU_HALF * TU_PITCH + e % TU_HALF] = src[e];
+  __syncthreads();
+  const uint32_t r = threadIdx.x % TU_ROWS;
+  if (r >= rows) return;
+  const uint64_t t = t0 + r;
+  const felt* raw = states + (t < bs ? t : bs) * TU_HALF;
+  for (uint32_t c = threadIdx.x / TU_ROWS; c < TU_HALF; c += TPB / TU_ROWS) {
+    const felt m = from_u64(tile[r * TU_PITCH + c]);
+    const felt v = add(raw[c], m);
+    out[(uint64_t)c * n + t] = v;
+    out[(uint64_t)(TU_HALF + c) * n + t] = m;
+    if (t == 0) first_last[c] = v;
+    if (t == n - 1) first_last[TU_HALF + c] = v;
+  }
+}
+
 // ---- GlobalUpdate column pairing. The transition constraints
 // k*next[i] - k*cur[i] - next[i+d] = 0 (src/aggregation/air.rs:101-119) fix
 // column d+i on rows 1..n-1 from column i, so as polynomials of degree < n
@@ -1306,6 +1455,19 @@ void launch_gu_trace(Prof& prof, hipStream_t s, const felt* masked, const felt* 
   LAUNCH(prof, "gu_trace_write", s, (double)n * 2 * GU_D_DEV * 16.0 + (double)ndev * GU_D_DEV * 16.0,
          hipLaunchKernelGGL(k_gu_tile_write, dim3(tiles, 2 * GU_D_DEV), dim3(TPB), 0, s, masked, raw, local, ndev,
                             kinv, n, tile_buf, out));
+}
+
+void launch_tu_states(Prof& prof, hipStream_t s, felt* states, const felt* x, const felt* xs, const felt* y,
+                      uint32_t bs, felt pr_inv, felt lr_inv, felt ac_inv) {
+  LAUNCH(prof, "tu_states", s, (double)bs * (2 * TU_FE + TU_AC + TU_HALF) * 16.0,
+         hipLaunchKernelGGL(k_tu_states, dim3(1), dim3(64), 0, s, states, x, xs, y, bs, pr_inv, lr_inv, ac_inv));
+}
+
+void launch_tu_write(Prof& prof, hipStream_t s, const uint64_t* masks, const felt* states, uint64_t bs, uint64_t n,
+                     felt* out, felt* first_last) {
+  LAUNCH(prof, "tu_trace", s, (double)n * TU_HALF * (8.0 + 32.0),
+         hipLaunchKernelGGL(k_tu_write, dim3((uint32_t)((n + TU_ROWS - 1) / TU_ROWS)), dim3(TPB), 0, s, masks,
+                            states, bs, n, out, first_last));
 }
 
 void launch_dt_eval_consts(Prof& prof, hipStream_t s, int air, const felt* cc, felt k, felt w_last, const felt* aval,

@@ -218,6 +218,17 @@ void launch_dt_draw_z(Prof& prof, hipStream_t s, uint32_t* seed, const uint32_t*
 // 60 * ceil(n / 4096) felts
 void launch_gu_trace(Prof& prof, hipStream_t s, const felt* masked, const felt* raw, const felt* local,
                      uint64_t ndev, felt kinv, uint64_t n, felt* tile_buf, felt* out);
+// TrainingUpdate trace (src/training/prover.rs:90-218). states: (bs + 1) x 120 felts
+// with row 0 = the initial state ([v, s] pairs, w row-major then b); launch_tu_states
+// fills rows 1..bs with the signed fixed-point SGD steps over x, xs (bs x 9) and y
+// (bs x 6), given the inverses of the precision, the learning rate and
+// f64_to_felt(6.0). launch_tu_write: row t of the 240 x n column-major trace =
+// [states[min(t, bs)] + masks[t] | masks[t]] from n x 120 row-major u64 masks;
+// first_last (240 felts) = the masked half of row 0, then of row n - 1
+void launch_tu_states(Prof& prof, hipStream_t s, felt* states, const felt* x, const felt* xs, const felt* y,
+                      uint32_t bs, felt pr_inv, felt lr_inv, felt ac_inv);
+void launch_tu_write(Prof& prof, hipStream_t s, const uint64_t* masks, const felt* states, uint64_t bs, uint64_t n,
+                     felt* out, felt* first_last);
 
 // ---------------------------------------------------------------- constraints
 // Points of a coset-major shard: local index q = c*n + t is cx[c] * w_n^t,

@@ -276,12 +276,46 @@ class TrainingUpdateProver(Prover):
             cols[:half, t] = pack([(r + m) % P for r, m in zip(raw, mrow)])
         return TraceTable(cols)
 
-    def get_pub_inputs(self, trace: TraceTable) -> TrainingUpdateInputs:
-        """prover.rs:236-270."""
-        half = trace.width() // 2
-        rows = trace.length()
+    def build_trace_device(self, ctx=None, d_out=None):
+        """build_trace() on the GPU (zkp_build_training_update_trace: the SGD chain and the
+        masked rows are computed there): returns the device pointer of the 240 x n
+        column-major trace in HBM (caller frees it with ctx.free; d_out = an existing
+        allocation of 240 * n * 16 bytes to reuse) and keeps the first and last masked
+        rows for get_pub_inputs(). The masks are build_trace()'s: the same trace."""
+        ctx = ctx or self.context()
+        n, half = self.trace_length, TU_STATE
+        initial = []
+        for row, srow in zip(self.initial_w, self.w_sign):
+            for v, s in zip(row, srow):
+                initial += [v % P, s % P]
+        for v, s in zip(self.initial_b, self.b_sign):
+            initial += [v % P, s % P]
+        rng = np.random.default_rng(self.mask_seed)
+        masks = rng.integers(0, 1 << 64, size=(n, half), dtype=np.uint64, endpoint=False)
+        d = d_out if d_out is not None else ctx.alloc(2 * half * n * 16)
+        try:
+            self._first_last = ctx.build_training_update_trace(
+                initial, self.x_batch, self.x_batch_sign, self.y_batch, self.learning_rate, self.precision,
+                masks, n, d)
+        except Exception:
+            if d_out is None:
+                ctx.free(d)
+            raise
+        return d
+
+    def get_pub_inputs(self, trace: TraceTable | None = None) -> TrainingUpdateInputs:
+        """prover.rs:236-270 (without a trace: the rows that build_trace_device() kept)."""
+        if trace is None:
+            if getattr(self, "_first_last", None) is None:
+                raise ValueError("get_pub_inputs() without a trace needs build_trace_device() first")
+            first, last = self._first_last
+        else:
+            half = trace.width() // 2
+            rows = trace.length()
+            first = [trace.get(c, 0) for c in range(half)]
+            last = [trace.get(c, rows - 1) for c in range(half)]
         return TrainingUpdateInputs(
-            [trace.get(c, 0) for c in range(half)], [trace.get(c, rows - 1) for c in range(half)],
+            list(first), list(last),
             self.trace_length - 1, [list(r) for r in self.x_batch], [list(r) for r in self.y_batch],
             self.learning_rate, self.precision, self.batch_size)
 
