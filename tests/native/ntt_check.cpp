@@ -7,8 +7,10 @@
 // here the inputs put p - 1 against small values so the first stages' sums land
 // in [p, 2^128) in every lane (dense) or in one lane of many (sparse), for the DIF
 // (natural in, bit-reversed out) and DIT (bit-reversed in, natural out, with and
-// without the coset scale) passes, 2^11 .. 2^18, several batches. Every output
-// is compared with a naive O(n^2) host DFT (2^11) or the host radix-2 NTT.
+// without the coset scale) passes, 2^11 .. 2^21, several batches: 45 cases, which
+// between them launch every k_ntt8 instantiation of ntt.hip's ZKP_NTT8_KERNELS and
+// the one-, two- and three-pass plans. Every output is compared with a naive
+// O(n^2) host DFT (2^11) or the host radix-2 NTT.
 // Prints one line per case and exits non-zero on any mismatch.
 #include <hip/hip_runtime.h>
 
@@ -116,7 +118,14 @@ int main() {
   Prof pf;
   const felt pm1 = make(0xffffd30000000000ull, 0xffffffffffffffffull);  // p - 1
   int bad = 0, cases = 0;
-  for (uint32_t logn : {11u, 13u, 18u, 19u, 20u}) {
+  // all three patterns at 2^11 (one pass), 2^13 (6 + 7) and 2^18 (11 + 7); the dense pattern
+  // (both directions, scaled DIT) for the kernels those leave out: 2^12 (6 + 6), 2^16 (8 + 8),
+  // 2^19-2^20 (11 + 8/9; 9 stages in 512-thread blocks from 8 batches) and 2^21 (6 + 8 + 7)
+  struct Case { uint32_t logn, batches; bool dense_only; };
+  for (const Case c : {Case{11, 3, false}, Case{12, 3, true}, Case{13, 3, false}, Case{16, 3, true},
+                       Case{18, 3, false}, Case{19, 2, true}, Case{20, 2, true}, Case{20, 8, true},
+                       Case{21, 2, true}}) {
+    const uint32_t logn = c.logn, batches = c.batches;
     const uint64_t n = 1ull << logn;
     const uint32_t logN = logn + 1;
     const std::vector<felt> twf = stage_table(logN, false), twi = stage_table(logN, true);
@@ -128,9 +137,7 @@ int main() {
     for (int dit = 0; dit < 2; dit++)
       for (int pattern = 0; pattern < 3; pattern++)
         for (int scaled = 0; scaled < (dit ? 2 : 1); scaled++) {
-          // 2^19-2^20 (the two-pass 11-stage plan): the dense pattern, both directions, scaled DIT
-          if (logn >= 19 && pattern != 0) continue;
-          const uint32_t batches = logn >= 19 ? 2 : 3;
+          if (c.dense_only && pattern != 0) continue;
           std::vector<felt> h((size_t)batches * n), S(scaled ? (size_t)2 * n : 0);
           for (uint32_t b = 0; b < batches; b++)
             for (uint64_t i = 0; i < n; i++) {

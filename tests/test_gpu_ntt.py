@@ -6,7 +6,9 @@ a round with the exact forms). Random data reaches those branches about once per
 2^32 operations, so the proof-level parity tests never take them; these native
 checks drive them on purpose (values at p - 1 against small values, products whose
 residue sits at the top of the range or below 2^128 - p) and compare with the host's
-portable arithmetic and a host DFT. Binaries built by __graft_entry__.build()
+portable arithmetic and a host DFT. ntt_check runs 45 cases (2^11 .. 2^21) that between
+them launch every k_ntt8 instantiation the pass plan can reach and the one-, two- and
+three-pass plans. Binaries built by __graft_entry__.build()
 (tests/native/Makefile)."""
 import os
 import subprocess

@@ -1,10 +1,9 @@
 // ntt.hip — the NTT kernels of the prover (gfx950): radix-8 register-blocked
-// LDS passes over stage-major twiddles, and their launch planning. Split from
+// LDS passes over stage-major twiddles, and their launches (planned in ntt_plan.hpp). Split from
 // kernels.hip so the hottest kernel rebuilds on its own.
 #include "kernels_common.hpp"
+#include "ntt_plan.hpp"
 
-#include <algorithm>
-#include <cstdlib>
 #include <mutex>
 
 using kc::static_for;
@@ -20,7 +19,7 @@ struct NttKArgs {
   const felt* tw;
   uint64_t src_stride, dst_stride;
   uint32_t src_div, scale_mod;
-  uint32_t logn, s0, K, lo, T, Tl, logT, logTl, tw_shift, dit;
+  uint32_t logn, s0, K, lo, T, Tl, logT, logTl, dit;
 };
 
 // One LDS pass of K radix-2 stages over T interleaved groups of 2^K elements.
@@ -99,10 +98,8 @@ struct Ntt8Args {
   const felt* tw;
   uint64_t src_stride, dst_stride;
   uint32_t src_div, scale_mod;
-  uint32_t logn, s0, K, lo, logT, logTl, tw_shift, nrounds;
-  uint32_t rbits[4];
+  uint32_t logn, s0, K, lo, logT, logTl;
   uint32_t tile_major;  // 1: deal whole position blocks to XCDs (k_ntt8)
-  uint32_t batches, items;  // k_ntt8_pipe: batches of the pass, tiles x batches
 };
 
 // stage-major twiddles: level t holds w_{2^(t+1)}^j at tw[(2^t - 1) + j]
@@ -215,26 +212,14 @@ __device__ __forceinline__ void bfly2(felt& x0, felt& y0, felt w0, felt& x1, fel
 // skipped. A template flag, so the other passes keep their register budget.
 // (5 waves/SIMD for the 6-stage passes spills 4-10 VGPRs and is slower:
 // profiles/r05_ab_ntt_5waves_not_adopted.txt)
-// LDS barrier of the passes: every wave's LDS operations retired, then s_barrier. No
-// vmcnt wait: the pipelined pass keeps its next tile's LDS-DMA loads in flight across
-// it (a __syncthreads() would drain them, cdna_hip_programming.md §5).
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-}
-
+//
 // One tile of a k_ntt8 pass (block-local elements (gg, q) of batch bidx, position block
-// `tile`) in the block's LDS `lds`. PIPE: round 0 reads the tile from `lds`, where
-// k_ntt8_pipe's LDS-DMA put it (the pass has no coset scale and loads directly).
-template <bool DIT, int NT, int KC, bool SMALL, bool PIPE = false>
+// `tile`) in the block's LDS `lds`.
+template <bool DIT, int NT, int KC, bool SMALL>
 __device__ __forceinline__ void ntt8_tile(const Ntt8Args& a, uint32_t bidx, uint32_t tile, felt* lds) {
   constexpr int E = NT * 8;
   constexpr uint32_t K = KC;
-  auto tile_barrier = [] {
-    if constexpr (PIPE) lds_barrier();
-    else __syncthreads();
-  };
-  constexpr uint32_t LOGNT = NT == 1024 ? 10 : (NT == 512 ? 9 : 8);
+  constexpr uint32_t LOGNT = NT == 512 ? 9 : 8;
   constexpr uint32_t logT = LOGNT + 3 - KC;  // E = NT * 8 elements per block
   constexpr uint32_t T = 1u << logT;
   static_assert(T == 1 || T >= 4, "the LDS swizzles take rows of 1 or >= 4 felts");
@@ -331,7 +316,7 @@ __device__ __forceinline__ void ntt8_tile(const Ntt8Args& a, uint32_t bidx, uint
     Rare q;
     stage_in(std::true_type{}, q);
     if (scale && q.any()) stage_in(std::false_type{}, q);
-    tile_barrier();
+    __syncthreads();
   }
   uint32_t b0 = DIT ? 0 : K;
   static_for<0, NttRounds<KC>::n>([&](auto rr) {
@@ -339,7 +324,7 @@ __device__ __forceinline__ void ntt8_tile(const Ntt8Args& a, uint32_t bidx, uint
     constexpr uint32_t rb = NttRounds<KC>::bits(r);
     if (!DIT) b0 -= rb;
     constexpr bool first = r == 0, last = r + 1 == NttRounds<KC>::n;
-    if (!first) tile_barrier();
+    if (!first) __syncthreads();
     felt x[8];
     uint32_t ggs[2], qlow[2];
     // block-local coordinates (gg, q) of register m in this round (for thread tr)
@@ -365,7 +350,7 @@ __device__ __forceinline__ void ntt8_tile(const Ntt8Args& a, uint32_t bidx, uint
     for (int m = 0; m < 8; m++) {
       uint32_t extra = m >> rb, bf = m & ((1u << rb) - 1);
       uint32_t c = (extra << LOGNT) | tr;
-      if (first && !staged && !PIPE) {  // straight from HBM (coalesced along gg), coset scale fused
+      if (first && !staged) {  // straight from HBM (coalesced along gg), coset scale fused
         uint32_t ad = gaddr(coord_gg(m, tr), coord_q(m, tr));
         felt v = NTT_LD(src + ad);
         if (scale) v = bmul<FAST>(v, NTT_LD(scale + ad), qq);
@@ -471,7 +456,7 @@ __device__ __forceinline__ void ntt8_tile(const Ntt8Args& a, uint32_t bidx, uint
     Rare qq;
     round(std::true_type{}, qq);
     if (qq.any()) round(std::false_type{}, qq);
-    if (!last || staged) tile_barrier();  // everyone has read this round's slots
+    if (!last || staged) __syncthreads();  // everyone has read this round's slots
 #pragma unroll
     for (int m = 0; m < 8; m++) {
       if (last && !staged) NTT_ST(dst + gaddr(coord_gg(m, tid), coord_q(m, tid)), x[m]);  // straight to HBM
@@ -480,7 +465,7 @@ __device__ __forceinline__ void ntt8_tile(const Ntt8Args& a, uint32_t bidx, uint
     if (DIT) b0 += rb;
   });
   if (staged) {  // LDS -> HBM in the contiguous order
-    tile_barrier();
+    __syncthreads();
 #pragma unroll
     for (int i = 0; i < 8; i++) {
       uint32_t slot;
@@ -509,55 +494,6 @@ __global__ __launch_bounds__(NT, (NT == 256 && KC == 11) ? 5 : 1) void k_ntt8(Nt
   ntt8_tile<DIT, NT, KC, SMALL>(a, bidx, tile, lds);
 }
 
-// The 9-stage pass in rows of 8 felts (512 threads, 4096 felts per tile) with direct loads
-// (2^20: DIT pass 2, DIF pass 1), software-pipelined: one persistent block per CU over the
-// pass's tiles (item = tile * batches + batch, batch fastest as in k_ntt8), two 64-KB LDS
-// buffers. While a tile's three rounds run, the next tile streams into the other buffer by
-// LDS-DMA (global_load_lds_dwordx4: no VGPRs held, so the rounds keep their registers);
-// the swizzle of k_ntt8's rows of 8 goes on the per-lane source address (the DMA writes a
-// wave's 1 KB lane-linearly).
-// TUNING BUILDS ONLY (ZKP_NTT_PIPE=1; not adopted): bit-exact, but
-// 1.68 against 1.51 ms for the C2 composition-shape LDE (profiles/r06_ab_ntt_pipe_not_adopted.txt).
-// The twiddle loads of the rounds are ordinary loads, beside which hipcc waits vmcnt(0) and
-// so drains the prefetch; and even with the loads perfectly hidden, one 512-thread block per
-// CU is 2 waves per SIMD, where the register-resident butterfly rate is 393 G/s against
-// 430 G/s at the 4 waves the library's pass keeps (tests/native/ubench_bfly --occ,
-// profiles/r06_ubench_bfly_occupancy.txt): no headroom left for the overlap to win.
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) void glob_void_t;
-template <bool DIT>
-__global__ __launch_bounds__(512) void k_ntt8_pipe(Ntt8Args a) {
-  extern __shared__ felt lds[];
-  constexpr uint32_t NT = 512, K = 9, E = 4096, LOGNT = 9;
-  const uint32_t B = a.batches, items = a.items, tid = threadIdx.x;
-  // LDS-DMA of item `it` into buf: instruction i of wave w fills slots [(8i + w) * 64, +64);
-  // slot s = P(q) * 8 + (gg ^ (q & 7)) (k_ntt8's rows-of-8 lidx, P(q) = q ^ ((q2 ^ q3) & 1),
-  // an involution), so lane L loads the element whose slot is its own
-  auto prefetch = [&](uint32_t it, felt* buf) {
-    const uint32_t bidx = it % B, tile = it / B;
-    const felt* src = a.src + (uint64_t)(bidx / a.src_div) * a.src_stride;
-    const uint32_t g0 = tile << 3, hi0 = g0 >> a.lo, l0 = g0 & ((1u << a.lo) - 1);
-    const uint32_t w = tid >> 6, L = tid & 63;
-#pragma unroll
-    for (uint32_t i = 0; i < 8; i++) {
-      const uint32_t s0 = (8 * i + w) * 64, sl = s0 + L, r = sl >> 3, c = sl & 7;
-      const uint32_t q = r ^ (((r >> 2) ^ (r >> 3)) & 1u), gg = c ^ (q & 7u);
-      const uint32_t ad = (hi0 << (a.lo + K)) + (q << a.lo) + l0 + gg;
-      __builtin_amdgcn_global_load_lds((glob_void_t*)(src + ad), (lds_void_t*)(buf + s0), 16, 0, 0);
-    }
-  };
-  uint32_t it = blockIdx.x;
-  if (it < items) prefetch(it, lds);
-  for (uint32_t k = 0; it < items; it += gridDim.x, k ^= 1) {
-    felt* cur = lds + k * E;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this tile's DMA (and the last tile's stores)
-    lds_barrier();  // every wave's DMA landed; every wave is past the other buffer's last reads
-    if (it + gridDim.x < items) prefetch(it + gridDim.x, lds + (k ^ 1) * E);
-    ntt8_tile<DIT, NT, K, false, true>(a, it % B, it / B, cur);
-  }
-  (void)LOGNT;
-}
-
 }  // namespace
 
 void preload_ntt_module() {
@@ -565,50 +501,10 @@ void preload_ntt_module() {
   (void)hipFuncGetAttributes(&fa, (const void*)k_ntt_pass);
 }
 
-std::vector<NttPass> ntt_plan(uint32_t logn, bool dit) {
-  const uint32_t KMAX = 8, LOGE = 12;
-  std::vector<NttPass> out;
-  if (logn == 0) return out;
-  uint32_t npass = (logn + KMAX - 1) / KMAX;
-  // pass sizes: prefer multiples of 3 (whole radix-8 rounds), largest pass last
-  uint32_t Ks[4] = {0, 0, 0, 0};
-  {
-    uint32_t rem = logn;
-    for (uint32_t p = 0; p < npass; p++) {
-      uint32_t left = npass - p;
-      uint32_t k = (rem + left - 1) / left;
-      if (left > 1) {
-        uint32_t k3 = k / 3 * 3;  // round down to whole radix-8 rounds if the rest still fits
-        if (k3 >= 3 && rem - k3 <= KMAX * (left - 1)) k = k3;
-      }
-      Ks[p] = k;
-      rem -= k;
-    }
-  }
-  uint32_t s0 = 0;
-  for (uint32_t p = 0; p < npass; p++) {
-    uint32_t K = Ks[p];
-    NttPass ps;
-    ps.logn = logn;
-    ps.s0 = s0;
-    ps.K = K;
-    ps.lo = dit ? s0 : logn - s0 - K;
-    uint32_t logG = logn - K;
-    uint32_t logT = LOGE - K < logG ? LOGE - K : logG;
-    uint32_t logTl = logT < ps.lo ? logT : ps.lo;
-    ps.T = 1u << logT;
-    ps.Tl = 1u << logTl;
-    out.push_back(ps);
-    s0 += K;
-  }
-  return out;
-}
-
 static void launch_ntt_radix2(Prof& prof, hipStream_t s, const NttBatch& b, uint32_t logn, bool dit,
-                              const felt* tw, uint32_t logN) {
-  auto plan = ntt_plan(logn, dit);
+                              const felt* tw) {
   bool first = true;
-  for (const auto& ps : plan) {
+  for (const NttPass& ps : ntt_plan(logn, dit, b.batches)) {
     NttKArgs a;
     a.src = first ? b.src : b.dst;
     a.dst = b.dst;
@@ -622,81 +518,82 @@ static void launch_ntt_radix2(Prof& prof, hipStream_t s, const NttBatch& b, uint
     a.s0 = ps.s0;
     a.K = ps.K;
     a.lo = ps.lo;
-    a.T = ps.T;
-    a.Tl = ps.Tl;
-    a.logT = kc::ilog2_u64(ps.T);
-    a.logTl = kc::ilog2_u64(ps.Tl);
-    a.tw_shift = logN - logn;
+    a.T = 1u << ps.logT;
+    a.Tl = 1u << ps.logTl;
+    a.logT = ps.logT;
+    a.logTl = ps.logTl;
     a.dit = dit ? 1 : 0;
     uint64_t groups = 1ull << (logn - ps.K);
-    dim3 grid((uint32_t)(groups / ps.T), b.batches);
-    size_t shmem = (size_t)(ps.T << ps.K) * sizeof(felt);
+    dim3 grid((uint32_t)(groups >> ps.logT), b.batches);
+    size_t shmem = (size_t)(a.T << ps.K) * sizeof(felt);
     LAUNCH(prof, dit ? "ntt_dit_r2" : "ntt_dif_r2", s, (double)b.batches * (1ull << logn) * 16.0 * (a.scale ? 3 : 2),
            hipLaunchKernelGGL(k_ntt_pass, grid, dim3(TPB), shmem, s, a));
     first = false;
   }
 }
 
-// radix-8 register-blocked passes: 256-thread blocks (E = 2048 elements, K <= 8)
-// for the big transforms (several blocks per CU overlap load and compute);
-// n must be >= 2^11.
-#ifndef ZKP_NTT_PIPE
-#define ZKP_NTT_PIPE 0  // tuning builds set 1 (k_ntt8_pipe for the 9-stage direct-load passes)
-#endif
-#ifndef ZKP_NTT_ONE_PASS_MAX
-#define ZKP_NTT_ONE_PASS_MAX 11  // (tuning builds set 13: see one_pass in launch_ntt)
-#endif
+// Every k_ntt8<DIT, NT, K, SMALL> that ntt_plan (ntt_plan.hpp) can ask for; a pass outside
+// this list is an error. tests/test_ntt_plan.py holds the same set against the plan.
+#define ZKP_NTT8_KERNELS(X)                                                                \
+  X(true, 256, 6, true) X(true, 256, 8, true) X(true, 256, 11, true)                       \
+  X(true, 256, 6, false) X(true, 256, 7, false) X(true, 256, 8, false)                     \
+  X(true, 256, 9, false) X(true, 512, 9, false)                                            \
+  X(false, 256, 6, true) X(false, 256, 7, true) X(false, 256, 8, true) X(false, 256, 11, true) \
+  X(false, 256, 6, false) X(false, 256, 7, false) X(false, 256, 8, false)                  \
+  X(false, 256, 9, false) X(false, 512, 9, false)
 
-uint32_t ntt_passes(uint32_t logn) {
-  if (logn < 11 || logn <= ZKP_NTT_ONE_PASS_MAX) return 1;
-  if (logn == 19 || logn == 20) return 2;
-#ifdef ZKP_NTT_PLAN22
-  if (logn == 21 || logn == 22) return ZKP_NTT_PLAN22 == 1165 ? 3 : 2;
-#endif
-#ifdef ZKP_NTT_KFIRST
-  if (logn >= 12 && logn <= 16 && logn - ZKP_NTT_KFIRST >= 5 && logn - ZKP_NTT_KFIRST <= 9) return 2;
-#endif
-  const uint32_t KMAX = (logn == 17 || logn == 18) ? 9 : 8;
-  return (logn + KMAX - 1) / KMAX;
-}
-
+// Transforms of >= 2^11 points: radix-8 register-blocked passes (k_ntt8), planned by
+// ntt_plan (ntt_plan.hpp). Why that plan:
+//
+// Passes of up to 8 stages in 256-thread blocks (2048 elements; several blocks per CU
+// overlap load and compute).
+// (10-stage passes for 2^19-2^20 — 512-thread blocks with rows of 4 felts, the
+// T = 4 layout of k_ntt8's lidx — measured slower than 6+6+8: DESIGN.md §4.)
+//
+// 2^19-2^20: two passes in 256-thread blocks, 11 stages over one contiguous
+// 2048-element group per block (the pass with lo = 0: rows of 1 felt, staged through
+// LDS) and the rest (8 or 9 stages) over 8 or 4 adjacent groups per block: 7 LDS rounds
+// as before (3+3+3+2 | 3+3(+3)) and a third less HBM traffic than 6+6+8
+// (tests/native/kbench_ntt.cpp: with the butterflies compiled out the 6+6+8 passes
+// take 1.13 of the 1.65 ms of a 48-array 2^20 LDE, about three copies of the data).
+//
+// Round 6: 2^17-2^18 as 11 + 6/7 too (instead of 9 + 8/9 in 512-thread blocks): the 11-stage
+// pass runs 5 waves per SIMD against the 9-stage pass's 4 (tests/native/kbench_ntt 18: the
+// 48-array LDE 0.368 -> 0.352 ms, the DIF 0.065 -> 0.057; profiles/r06_ab_ntt_11_7_2e18.txt;
+// the 9 + 8/9 plan was measured and removed).
+//
+// 2^11: the whole transform in one 11-stage pass (one array per 256-thread block, rows
+// of 1 felt): one HBM read and write per array instead of 6 + 5 stages' two.
+// (2^13 in one 1024-thread pass — 128 KB of LDS, one block per CU — was slower than
+// 6 + 7 on the reference's TrainingUpdate proof, 2^13 x 240 at blowup 16: ntt_dit
+// 0.76 -> 0.83 ms per proof, BENCH reference_flow.training_proof_profile; the 12- and
+// 13-stage kernels were measured and removed, as were a 5/7/8-stage lo = 0 pass for
+// 2^12-2^16, profiles/r06_kbench_ntt13_plans.txt, and 2^21-2^22 in two passes or as
+// 11 + 6 + 5/4, profiles/r06_ab_ntt_two_pass_2e22_not_adopted.txt.)
+//
+// 9 stages: 512 threads x 8 = 4096 elements, rows of 8 felts = whole 128-B lines
+// (64 KB: 2 blocks per CU, the same 4 waves per SIMD as the 256-thread 9-stage pass,
+// whose 64-B runs cost 1.7x their bytes in L2 fetches: profiles/r05_ab_ntt_k512_tmaj.txt);
+// 11 stages: 256-thread blocks of one group (rows of 1)
+// (2^20 with < 8 arrays, e.g. a sharded rank's 2-column interpolation rounds beside
+// its LDE: the 64-KB blocks wait for LDS next to the other stream's kernels — C5 rank
+// ntt_dif 0.75 -> 2.04 ms, profiles/r05_ab_rank_c5_ntt9.txt — so those keep 256 threads)
+// (That pass software-pipelined, one persistent block per CU loading its next tile by
+// LDS-DMA, was bit-exact but slower, 1.68 against 1.51 ms for the C2 composition-shape LDE;
+// measured and removed: profiles/r06_ab_ntt_pipe_not_adopted.txt)
+//
+// 7 stages beside an 11-stage pass (2^18): 256-thread blocks, rows of 16 felts (the DIF
+// rounds take lidx's rows-of-16 DIF swizzle; 512-thread blocks with rows of 32 were
+// measured and removed: the DIF pass 0.0571 -> 0.0606 ms at 2^18 x 6 arrays, half as
+// many workgroups, DIT unchanged: profiles/r06_kbench_ntt_k7.txt)
 void launch_ntt(Prof& prof, hipStream_t s, const NttBatch& b, uint32_t logn, bool dit, const felt* tw,
                 uint32_t logN, int only_pass) {
-  const uint32_t LOGE = 11;
-  // passes of up to KMAX stages. 2^17-2^18 run two passes of <= 9 stages instead
-  // of three: 9-stage passes use 512-thread blocks of 4096 elements (64 KB LDS,
-  // 2 blocks per CU = the same 4 waves/SIMD as 256-thread blocks; strided groups
-  // still load 8-felt runs), a third less HBM traffic for the same rounds.
-  // (10-stage passes for 2^19-2^20 — 512-thread blocks with rows of 4 felts, the
-  // T = 4 layout of k_ntt8's lidx — measured slower than 6+6+8: DESIGN.md §4.)
-  const uint32_t KMAX = (logn == 17 || logn == 18) ? 9 : 8;
-  // 2^19-2^20: two passes in 256-thread blocks, 11 stages over one contiguous
-  // 2048-element group per block (the pass with lo = 0: rows of 1 felt, staged through
-  // LDS) and the rest (8 or 9 stages) over 8 or 4 adjacent groups per block: 7 LDS rounds
-  // as before (3+3+3+2 | 3+3(+3)) and a third less HBM traffic than 6+6+8
-  // (tests/native/kbench_ntt.cpp: with the butterflies compiled out the 6+6+8 passes
-  // take 1.13 of the 1.65 ms of a 48-array 2^20 LDE, about three copies of the data).
-  // Round 6: 2^17-2^18 as 11 + 6/7 too (instead of 9 + 8/9 in 512-thread blocks): the 11-stage
-  // pass runs 5 waves per SIMD against the 9-stage pass's 4 (tests/native/kbench_ntt 18: the
-  // 48-array LDE 0.368 -> 0.352 ms, the DIF 0.065 -> 0.057; profiles/r06_ab_ntt_11_7_2e18.txt)
-#ifndef ZKP_NTT_TWO11_LOW
-#define ZKP_NTT_TWO11_LOW 1  // tuning builds set 0: the 9 + 8/9 plan
-#endif
-  const bool two11 = logn == 19 || logn == 20 || (ZKP_NTT_TWO11_LOW && (logn == 17 || logn == 18));
-  // 2^11: the whole transform in one 11-stage pass (one array per 256-thread block, rows
-  // of 1 felt): one HBM read and write per array instead of 6 + 5 stages' two.
-  // (2^13 in one 1024-thread pass — 128 KB of LDS, one block per CU — was slower than
-  // 6 + 7 on the reference's TrainingUpdate proof, 2^13 x 240 at blowup 16: ntt_dit
-  // 0.76 -> 0.83 ms per proof, BENCH reference_flow.training_proof_profile; the 12- and
-  // 13-stage kernels stay for tuning builds, ZKP_NTT_ONE_PASS_MAX)
-  const bool one_pass = logn >= 11 && logn <= ZKP_NTT_ONE_PASS_MAX;
   if (logN > 28)  // k_ntt8 indexes arrays and twiddles with 32-bit element offsets
     launch_fail(ZKP_ERR_TRACE_SHAPE, "NTT domain over 2^28 points (n * blowup)");
-  if (logn < LOGE) {
-    if (only_pass <= 0) launch_ntt_radix2(prof, s, b, logn, dit, tw, logN);
+  if (logn < 11) {
+    if (only_pass <= 0) launch_ntt_radix2(prof, s, b, logn, dit, tw);
     return;
   }
-  uint32_t npass = one_pass ? 1 : two11 ? 2 : (logn + KMAX - 1) / KMAX;
   // the dynamic-LDS attributes are per device: set them once for each device this
   // process launches on (threads of an in-process group drive different devices)
   static std::mutex attr_mu;
@@ -706,110 +603,17 @@ void launch_ntt(Prof& prof, hipStream_t s, const NttBatch& b, uint32_t logn, boo
   {
   std::lock_guard<std::mutex> attr_lock(attr_mu);
   if (!(attr_devs >> (dev & 63) & 1)) {
-    size_t maxb = (size_t)(1u << LOGE) * sizeof(felt);
-    const void* fns[] = {
-        (const void*)k_ntt8<true, 256, 5, false>,  (const void*)k_ntt8<true, 256, 6, false>,
-        (const void*)k_ntt8<true, 256, 7, false>,  (const void*)k_ntt8<true, 256, 8, false>,
-        (const void*)k_ntt8<false, 256, 5, false>, (const void*)k_ntt8<false, 256, 6, false>,
-        (const void*)k_ntt8<false, 256, 7, false>, (const void*)k_ntt8<false, 256, 8, false>,
-        (const void*)k_ntt8<true, 256, 5, true>,   (const void*)k_ntt8<true, 256, 6, true>,
-        (const void*)k_ntt8<true, 256, 7, true>,   (const void*)k_ntt8<true, 256, 8, true>,
-        (const void*)k_ntt8<false, 256, 5, true>,  (const void*)k_ntt8<false, 256, 6, true>,
-        (const void*)k_ntt8<false, 256, 7, true>,  (const void*)k_ntt8<false, 256, 8, true>,
-        (const void*)k_ntt8<true, 256, 9, false>,  (const void*)k_ntt8<false, 256, 9, false>,
-        (const void*)k_ntt8<true, 256, 11, true>,  (const void*)k_ntt8<false, 256, 11, true>,
-        (const void*)k_ntt8<true, 256, 9, true>,   (const void*)k_ntt8<false, 256, 9, true>,
-        (const void*)k_ntt8<true, 256, 11, false>, (const void*)k_ntt8<false, 256, 11, false>};
-    for (const void* f : fns) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxb);
-    const void* k9[] = {(const void*)k_ntt8<true, 512, 9, false>,  (const void*)k_ntt8<false, 512, 9, false>,
-                        (const void*)k_ntt8<true, 512, 9, true>,   (const void*)k_ntt8<false, 512, 9, true>};
-    for (const void* f : k9) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 4096 * 16);
-    const void* k7[] = {(const void*)k_ntt8<true, 512, 7, false>, (const void*)k_ntt8<false, 512, 7, false>,
-                        (const void*)k_ntt8<true, 512, 7, true>, (const void*)k_ntt8<false, 512, 7, true>};
-    for (const void* f : k7) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 4096 * 16);
-    const void* k12[] = {(const void*)k_ntt8<true, 512, 12, true>, (const void*)k_ntt8<false, 512, 12, true>};
-    for (const void* f : k12) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 4096 * 16);
-#ifdef ZKP_NTT_PLAN22
-    const void* k10[] = {(const void*)k_ntt8<true, 512, 10, false>, (const void*)k_ntt8<false, 512, 10, false>,
-                         (const void*)k_ntt8<true, 512, 10, true>, (const void*)k_ntt8<false, 512, 10, true>};
-    for (const void* f : k10) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 4096 * 16);
-#endif
-#if ZKP_NTT_PIPE
-    const void* kp[] = {(const void*)k_ntt8_pipe<true>, (const void*)k_ntt8_pipe<false>};
-    for (const void* f : kp) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4096 * 16);
-#endif
-    const void* k13[] = {(const void*)k_ntt8<true, 1024, 13, true>, (const void*)k_ntt8<false, 1024, 13, true>};
-    for (const void* f : k13) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 8192 * 16);
+#define X(D, NT, KK, S) \
+  (void)hipFuncSetAttribute((const void*)k_ntt8<D, NT, KK, S>, hipFuncAttributeMaxDynamicSharedMemorySize, NT * 8 * 16);
+    ZKP_NTT8_KERNELS(X)
+#undef X
     attr_devs |= 1ull << (dev & 63);
   }
   }
-  // pass sizes: prefer multiples of 3 (whole radix-8 rounds), largest pass last
-  uint32_t Ks[4] = {0, 0, 0, 0};
-#ifdef ZKP_NTT_PLAN22  // tuning builds only (tests/native kbench22): 2^21-2^22 in two passes, 12 + 9/10 or 11 + 10/11
-  if ((logn == 21 || logn == 22) && ZKP_NTT_PLAN22 == 1165) {  // 11 + 6 + 5/4
-    npass = 3;
-    const uint32_t k1 = 6, k2 = logn - 17;
-    Ks[0] = dit ? 11 : k2;
-    Ks[1] = k1;
-    Ks[2] = dit ? k2 : 11;
-  } else if (logn == 21 || logn == 22) {
-    npass = 2;
-    const uint32_t k0 = ZKP_NTT_PLAN22 == 1210 ? 12 : 11;  // the lo = 0 pass
-    Ks[0] = dit ? k0 : logn - k0;
-    Ks[1] = dit ? logn - k0 : k0;
-  } else
-#endif
-#ifdef ZKP_NTT_KFIRST  // tuning builds only (tests/native kbench13): the lo = 0 pass takes KFIRST stages
-  if (!one_pass && !two11 && logn >= 12 && logn <= 16 && logn - ZKP_NTT_KFIRST >= 5 && logn - ZKP_NTT_KFIRST <= 9) {
-    npass = 2;
-    Ks[0] = dit ? ZKP_NTT_KFIRST : logn - ZKP_NTT_KFIRST;
-    Ks[1] = dit ? logn - ZKP_NTT_KFIRST : ZKP_NTT_KFIRST;
-  } else
-#endif
-  if (one_pass) {
-    Ks[0] = logn;
-  } else if (two11) {  // the 11-stage pass is the one with lo = 0: first for DIT, last for DIF
-    Ks[0] = dit ? 11 : logn - 11;
-    Ks[1] = dit ? logn - 11 : 11;
-  } else {
-    uint32_t rem = logn;
-    for (uint32_t p = 0; p < npass; p++) {
-      uint32_t left = npass - p;
-      uint32_t k = (rem + left - 1) / left;
-      if (left > 1) {
-        uint32_t k3 = k / 3 * 3;  // round down to whole radix-8 rounds if the rest still fits
-        if (k3 >= 3 && rem - k3 <= KMAX * (left - 1)) k = k3;
-      }
-      Ks[p] = k;
-      rem -= k;
-    }
-  }
-  if (npass != ntt_passes(logn)) launch_fail(ZKP_ERR_DEVICE, "internal: NTT pass count");
-  uint32_t s0 = 0;
-  for (uint32_t p = 0; p < npass; s0 += Ks[p], p++) {
-    uint32_t K = Ks[p];
+  const NttPlan plan = ntt_plan(logn, dit, b.batches);
+  for (uint32_t p = 0; p < plan.n; p++) {
+    const NttPass& ps = plan.pass[p];
     if (only_pass >= 0 && (uint32_t)only_pass != p) continue;
-    // 9 stages: 512 threads x 8 = 4096 elements, rows of 8 felts = whole 128-B lines
-    // (64 KB: 2 blocks per CU, the same 4 waves per SIMD as the 256-thread 9-stage pass,
-    // whose 64-B runs cost 1.7x their bytes in L2 fetches: profiles/r05_ab_ntt_k512_tmaj.txt);
-    // 11 stages: 256-thread blocks of one group (rows of 1)
-    // (2^19-2^20 with < 8 arrays, e.g. a sharded rank's 2-column interpolation rounds beside
-    // its LDE: the 64-KB blocks wait for LDS next to the other stream's kernels — C5 rank
-    // ntt_dif 0.75 -> 2.04 ms, profiles/r05_ab_rank_c5_ntt9.txt — so those keep 256 threads)
-    // 7 stages beside an 11-stage pass (2^18): 256-thread blocks, rows of 16 felts (the DIF
-    // rounds take lidx's rows-of-16 DIF swizzle)
-#ifdef ZKP_NTT_K7_512
-    // tuning builds: 2^18's 7-stage pass in 512-thread blocks (rows of 32, no LDS bank
-    // conflicts) -- the DIF pass measured 0.0571 -> 0.0606 ms at 2^18 x 6 arrays (half as
-    // many workgroups), DIT unchanged: profiles/r06_kbench_ntt_k7.txt
-    const bool k7_512 = K == 7 && two11 && logn == 18;
-#else
-    const bool k7_512 = false;
-#endif
-    const uint32_t lognt = one_pass ? logn - 3
-                           : (K == 12 || K == 10 || k7_512) ? 9
-                           : K == 9 && (!two11 || b.batches >= 8) ? 9 : 8,
-                   loge = lognt + 3;
     Ntt8Args a;
     bool first = p == 0;
     a.src = first ? b.src : b.dst;
@@ -821,28 +625,17 @@ void launch_ntt(Prof& prof, hipStream_t s, const NttBatch& b, uint32_t logn, boo
     a.src_div = first ? b.src_div : 1;
     a.scale_mod = b.scale_mod ? b.scale_mod : 1;
     a.logn = logn;
-    a.s0 = s0;
-    a.K = K;
-    a.lo = dit ? s0 : logn - s0 - K;
-    a.logT = loge - K;
-    a.logTl = a.logT < a.lo ? a.logT : a.lo;
-    a.tw_shift = logN - logn;
-    // rounds of <= 3 bits, larger first
-    uint32_t nr = (K + 2) / 3, rem = K;
-    a.nrounds = nr;
-    for (uint32_t r = 0; r < 4; r++) a.rbits[r] = 0;
-    for (uint32_t r = 0; r < nr; r++) {
-      uint32_t rb = rem / (nr - r) + (rem % (nr - r) ? 1 : 0);
-      if (rb > 3) rb = 3;
-      a.rbits[r] = rb;
-      rem -= rb;
-    }
-    uint64_t groups = 1ull << (logn - K);
+    a.s0 = ps.s0;
+    a.K = ps.K;
+    a.lo = ps.lo;
+    a.logT = ps.logT;
+    a.logTl = ps.logTl;
+    uint64_t groups = 1ull << (logn - ps.K);
     dim3 grid(b.batches, (uint32_t)(groups >> a.logT));  // batch fastest (see k_ntt8)
     // the coset LDE's first pass reads each coefficient row for 8 cosets: whole position
     // blocks per XCD (k_ntt8) keep those reads, and the scale rows, to one fetch
     a.tile_major = first && b.src_div > 1 && grid.y % 8 == 0;
-    size_t shmem = (size_t)(1u << K) * (1u << a.logT) * sizeof(felt);
+    size_t shmem = (size_t)(1u << ps.K) * (1u << a.logT) * sizeof(felt);
     // compulsory bytes of this launch: every distinct input array once (the
     // coefficient arrays are shared by src_div coset batches, the scale table
     // has scale_mod rows) + every output once
@@ -850,63 +643,14 @@ void launch_ntt(Prof& prof, hipStream_t s, const NttBatch& b, uint32_t logn, boo
     const uint32_t src_arrays = first ? (b.batches + a.src_div - 1) / a.src_div : b.batches;
     const uint32_t scale_rows = a.scale ? (a.scale_mod < b.batches ? a.scale_mod : b.batches) : 0;
     const double bytes = arr * ((double)src_arrays + scale_rows + b.batches);
-    // the pass over stages 0..2 (lo = 0): the trivial-twiddle variant
-    const bool small = a.lo == 0;
-    a.batches = b.batches;
-    a.items = grid.x * grid.y;
-#if ZKP_NTT_PIPE
-    // the 9-stage direct-load pass in rows of 8, software-pipelined (k_ntt8_pipe): one
-    // persistent block per CU
-    if (K == 9 && lognt == 9 && !a.scale && a.logT == 3 && a.logTl == 3 && !a.tile_major) {
-      static int cus = 0;
-      if (!cus) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      const uint32_t blocks = std::min<uint32_t>(a.items, cus > 0 ? (uint32_t)cus : 256u);
-      LAUNCH(prof, dit ? "ntt_dit" : "ntt_dif", s, bytes,
-             if (dit) hipLaunchKernelGGL(k_ntt8_pipe<true>, dim3(blocks), dim3(512), 2 * shmem, s, a);
-             else hipLaunchKernelGGL(k_ntt8_pipe<false>, dim3(blocks), dim3(512), 2 * shmem, s, a));
-      continue;
-    }
-#endif
-#define ZKP_NTT8(D, NTT, KK)                                                                                   \
-  LAUNCH(prof, D ? "ntt_dit" : "ntt_dif", s, bytes,                                                           \
-         if (small) hipLaunchKernelGGL((k_ntt8<D, NTT, KK, true>), grid, dim3(NTT), shmem, s, a);              \
-         else hipLaunchKernelGGL((k_ntt8<D, NTT, KK, false>), grid, dim3(NTT), shmem, s, a))
-    switch (K * 2 + (dit ? 1 : 0)) {
-      case 11: ZKP_NTT8(true, 256, 5); break;
-      case 13: ZKP_NTT8(true, 256, 6); break;
-      case 15: if (lognt == 9) ZKP_NTT8(true, 512, 7); else ZKP_NTT8(true, 256, 7); break;
-      case 17: ZKP_NTT8(true, 256, 8); break;
-      case 10: ZKP_NTT8(false, 256, 5); break;
-      case 12: ZKP_NTT8(false, 256, 6); break;
-      case 14: if (lognt == 9) ZKP_NTT8(false, 512, 7); else ZKP_NTT8(false, 256, 7); break;
-      case 16: ZKP_NTT8(false, 256, 8); break;
-      case 19: if (lognt == 8) ZKP_NTT8(true, 256, 9); else ZKP_NTT8(true, 512, 9); break;
-      case 18: if (lognt == 8) ZKP_NTT8(false, 256, 9); else ZKP_NTT8(false, 512, 9); break;
-#ifdef ZKP_NTT_PLAN22
-      case 21: ZKP_NTT8(true, 512, 10); break;
-      case 20: ZKP_NTT8(false, 512, 10); break;
-      case 23: ZKP_NTT8(true, 256, 11); break;
-      case 22: ZKP_NTT8(false, 256, 11); break;
-#else
-      case 23: if (!small) launch_fail(ZKP_ERR_DEVICE, "internal: 11-stage NTT pass off lo = 0");
-               ZKP_NTT8(true, 256, 11); break;
-      case 22: if (!small) launch_fail(ZKP_ERR_DEVICE, "internal: 11-stage NTT pass off lo = 0");
-               ZKP_NTT8(false, 256, 11); break;
-#endif
-      case 25: if (!small) launch_fail(ZKP_ERR_DEVICE, "internal: 12-stage NTT pass off lo = 0");
-               LAUNCH(prof, "ntt_dit", s, bytes,
-                      hipLaunchKernelGGL((k_ntt8<true, 512, 12, true>), grid, dim3(512), shmem, s, a)); break;
-      case 24: if (!small) launch_fail(ZKP_ERR_DEVICE, "internal: 12-stage NTT pass off lo = 0");
-               LAUNCH(prof, "ntt_dif", s, bytes,
-                      hipLaunchKernelGGL((k_ntt8<false, 512, 12, true>), grid, dim3(512), shmem, s, a)); break;
-      case 27: if (!small) launch_fail(ZKP_ERR_DEVICE, "internal: 13-stage NTT pass off lo = 0");
-               LAUNCH(prof, "ntt_dit", s, bytes,
-                      hipLaunchKernelGGL((k_ntt8<true, 1024, 13, true>), grid, dim3(1024), shmem, s, a)); break;
-      case 26: if (!small) launch_fail(ZKP_ERR_DEVICE, "internal: 13-stage NTT pass off lo = 0");
-               LAUNCH(prof, "ntt_dif", s, bytes,
-                      hipLaunchKernelGGL((k_ntt8<false, 1024, 13, true>), grid, dim3(1024), shmem, s, a)); break;
-      default: launch_fail(ZKP_ERR_DEVICE, "internal: NTT pass of an unplanned size");
-    }
-#undef ZKP_NTT8
+    const uint32_t nt = 1u << ps.lognt;
+#define X(D, NT, KK, S)                                                              \
+  if (dit == D && nt == NT && ps.K == KK && ps.small == S)                           \
+    LAUNCH(prof, D ? "ntt_dit" : "ntt_dif", s, bytes,                                \
+           hipLaunchKernelGGL((k_ntt8<D, NT, KK, S>), grid, dim3(NT), shmem, s, a)); \
+  else
+    ZKP_NTT8_KERNELS(X)
+    launch_fail(ZKP_ERR_DEVICE, "internal: NTT pass of an unplanned size");
+#undef X
   }
 }

@@ -45,14 +45,8 @@ void preload_ntt_module();
 void warm_stream(hipStream_t s);
 
 // ---------------------------------------------------------------- NTT
-// One LDS pass of K radix-2 stages (see kernels.hip). `dit` = bit-reversed in
-// -> natural out (Cooley-Tukey); otherwise natural in -> bit-reversed out
-// (Gentleman-Sande). Stages [s0, s0+K).
-struct NttPass {
-  uint32_t logn, s0, K, lo, T, Tl;
-};
-std::vector<NttPass> ntt_plan(uint32_t logn, bool dit);
-
+// `dit` = bit-reversed in -> natural out (Cooley-Tukey); otherwise natural in ->
+// bit-reversed out (Gentleman-Sande). The passes of a transform: ntt_plan.hpp.
 struct NttBatch {
   const felt* src;     // batch b reads src + (b / src_div) * src_stride
   felt* dst;           // batch b writes dst + b * dst_stride
@@ -64,12 +58,11 @@ struct NttBatch {
 // Full transform over `batches` arrays of size 2^logn using the stage-major
 // twiddle table tw (level t at tw[2^t - 1 .. 2^(t+1) - 1) holds w_{2^(t+1)}^j;
 // forward table for DIT, inverse table for DIF).
-// only_pass >= 0: launch that pass of the plan alone (a caller pipelining the passes of
-// several batches over two streams: pass 1 of batch k+1 beside pass 2 of batch k);
-// ntt_passes(logn) = the number of passes of the plan (1 for the radix-2 path)
+// only_pass >= 0: launch that pass of ntt_plan(logn, dit, batches) alone (the timing
+// harness tests/native/kbench_ntt.cpp times the passes one by one; the library always
+// runs the whole plan). The radix-2 path (n < 2^11) counts as pass 0.
 void launch_ntt(Prof& prof, hipStream_t s, const NttBatch& b, uint32_t logn, bool dit, const felt* tw,
                 uint32_t logN, int only_pass = -1);
-uint32_t ntt_passes(uint32_t logn);
 
 // ---------------------------------------------------------------- tables
 // fill levels 0..top-1 of a stage-major table whose level `top` is present
