@@ -64,7 +64,17 @@ enum { ZKP_FIELD_EXTENSION_NONE = 1 };
 /* winterfell `ProofOptions::new(num_queries, blowup_factor, grinding_factor,
  * field_extension, fri_folding_factor, fri_remainder_max_degree,
  * batching_constraints, batching_deep)`; the reference's set is
- * (40, 16, 21, None, 16, 7, Algebraic, Algebraic) at src/main.rs:98-107. */
+ * (40, 16, 21, None, 16, 7, Algebraic, Algebraic) at src/main.rs:98-107.
+ *
+ * Accepted: num_queries 1..255, blowup_factor a power of two in 2..128 and at
+ * least the AIR's constraint-evaluation blowup, grinding_factor 0..32,
+ * fri_folding_factor 16, fri_remainder_max_degree 2^k - 1 <= 255. The FRI layers
+ * must also fit the trace: with L the number of layers (the domain n * blowup_factor
+ * is divided by 16 while it exceeds (fri_remainder_max_degree + 1) * blowup_factor),
+ * a trace of n rows needs n >= 16^L, so that the remainder has at least one
+ * coefficient. Shapes past that (n = 64, blowup 8, remainder degree 0) have no
+ * verifying proof: the prover, session and channel entries return
+ * ZKP_ERR_INVALID_OPTIONS and zkp_verify ZKP_VERIFY_UNACCEPTABLE_OPTIONS. */
 typedef struct zkp_proof_options {
   uint32_t num_queries;
   uint32_t blowup_factor;

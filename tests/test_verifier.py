@@ -11,6 +11,7 @@ import random
 import pytest
 
 import oracle_ref as O
+from option_cases import METHOD_PAIRS, MIMC_REMAINDER_SHAPES, REFUSED_SHAPES, fri_layers, options
 from zk_stark_project_amd import (AIR_GLOBAL_UPDATE, AIR_MIMC, AIR_TRAINING_UPDATE, GlobalUpdateProver, MimcAir,
                                   MimcInputs, ProofOptions, verify)
 from zk_stark_project_amd._native import VerifierError, verify_status
@@ -119,3 +120,92 @@ def test_invalid_trace_proof_rejected():
     pub = [vals[0], vals[-1]]
     proof, _ = O.prove(AIR_MIMC, bytes(tr), 1, 128, to_bytes(pub), opts)
     assert verify_status(AIR_MIMC, proof, pub, opts) != 0
+
+
+# ---------------------------------------------------------------- option space
+
+
+@pytest.mark.parametrize("n,blowup,r", MIMC_REMAINDER_SHAPES)
+def test_accepts_oracle_proofs_over_remainder_degrees(n, blowup, r):
+    """Every remainder degree / FRI depth of the GPU option matrix, with and without grinding."""
+    for grind in (4, 0):
+        opts = options(20, blowup, grind, r)
+        proof, pub = mimc_case(n, opts)
+        assert O.verify(AIR_MIMC, proof, to_bytes(pub), opts) == 0
+        assert verify_status(AIR_MIMC, proof, pub, opts) == 0
+
+
+@pytest.mark.parametrize("blowup", [2, 16])
+def test_accepts_global_update_without_fri_layers(blowup):
+    """GlobalUpdate n = 8: L = 0, the whole LDE domain is the remainder."""
+    opts = options(20, blowup, 4)
+    p = gu(2, 8, 2, opts)
+    t = p.build_trace()
+    pub = p.get_pub_inputs(t).to_elements()
+    proof, tr = O.prove(AIR_GLOBAL_UPDATE, t.to_bytes(), 120, 8, to_bytes(pub), opts)
+    assert tr.num_fri_layers == 0
+    assert O.verify(AIR_GLOBAL_UPDATE, proof, to_bytes(pub), opts) == 0
+    assert verify_status(AIR_GLOBAL_UPDATE, proof, pub, opts) == 0
+
+
+@pytest.mark.parametrize("constraints,deep", METHOD_PAIRS)
+def test_accepts_oracle_proofs_over_batching_methods(constraints, deep):
+    opts = options(20, 8, 4, 7, constraints, deep)
+    proof, pub = mimc_case(256, opts)
+    assert O.verify(AIR_MIMC, proof, to_bytes(pub), opts) == 0
+    assert verify_status(AIR_MIMC, proof, pub, opts) == 0
+    if (constraints, deep) != (1, 1):  # the methods are part of the accepted options
+        assert verify_status(AIR_MIMC, proof, pub, options(20, 8, 4)) == 33
+
+
+@pytest.mark.parametrize("r", [0, 255])
+def test_rejects_mutations_at_remainder_edges(r):
+    """Single-bit mutations of a proof with a one-coefficient remainder (r = 0, L = 2)
+    and of one with no FRI layer (r = 255): both verifiers reject each."""
+    opts = options(20, 8, 4, r)
+    proof, pub = mimc_case(256, opts)
+    assert verify_status(AIR_MIMC, proof, pub, opts) == 0
+    rnd = random.Random(11 + r)
+    for _ in range(40):
+        bad = bytearray(proof)
+        bad[rnd.randrange(0, len(bad))] ^= 1 << rnd.randrange(8)
+        assert verify_status(AIR_MIMC, bytes(bad), pub, opts) != 0
+        assert O.verify(AIR_MIMC, bytes(bad), to_bytes(pub), opts) != 0
+
+
+R_BYTE = 28  # Context: width, 0, 0, log n, u16 0, 16, modulus (16 B), q, B, g, ext, F, then r
+
+
+def refused_case(air, n, blowup, r):
+    """A proof that states a refused shape: the oracle refuses to make one, so a proof
+    of the same trace at r = 7 gets the remainder-degree byte of its context patched."""
+    ok = options(20, blowup, 4)
+    if air == AIR_MIMC:
+        proof, pub = mimc_case(n, ok)
+    else:
+        p = gu(2, n, 2, ok)
+        t = p.build_trace()
+        pub = p.get_pub_inputs(t).to_elements()
+        proof, _ = O.prove(air, t.to_bytes(), 120, n, to_bytes(pub), ok)
+    assert proof[R_BYTE] == 7 and proof[R_BYTE - 4] == blowup
+    bad = bytearray(proof)
+    bad[R_BYTE] = r
+    return bytes(bad), pub
+
+
+@pytest.mark.parametrize("air,n,blowup,r", REFUSED_SHAPES)
+def test_fri_layers_past_the_trace_are_unacceptable(air, n, blowup, r):
+    """16^L > n: zkp_verify answers UnacceptableProofOptions for a proof that states such
+    options (even when the caller accepts them), and zkp_channel_create refuses the shape."""
+    from zk_stark_project_amd._native import Channel, ZkpError
+    opts = options(20, blowup, 4, r)
+    proof, pub = refused_case(air, n, blowup, r)
+    assert verify_status(air, proof, pub, opts) == 33
+    with pytest.raises(VerifierError) as e:
+        verify(air, proof, pub, opts)
+    assert e.value.kind == "UnacceptableProofOptions"
+    assert O.verify(air, proof, to_bytes(pub), opts) != 0
+    with pytest.raises(ZkpError) as e:
+        Channel(air, 120 if air == AIR_GLOBAL_UPDATE else 1, n, pub, opts)
+    assert e.value.code == 1  # ZKP_ERR_INVALID_OPTIONS
+    Channel(air, 120 if air == AIR_GLOBAL_UPDATE else 1, n, pub, options(20, blowup, 4)).close()

@@ -266,6 +266,29 @@ inline int check_options(const zkp_proof_options* o) {
   return 0;
 }
 
+// FRI layer count over an LDE domain of N points (FriOptions::num_fri_layers)
+inline uint32_t fri_num_layers(uint64_t N, const zkp_proof_options* o) {
+  uint32_t L = 0;
+  const uint64_t maxrem = (uint64_t)(o->fri_remainder_max_degree + 1) * o->blowup_factor;
+  while (N > maxrem) { N /= o->fri_folding_factor; L++; }
+  return L;
+}
+
+// The FRI layers must fit the trace: F^L <= n, i.e. the remainder domain N / F^L
+// holds at least blowup_factor points and the remainder has a coefficient. A
+// small fri_remainder_max_degree on a short trace breaks it (n = 64, B = 8,
+// r = 0: 512 -> 32 -> 2); the last layer would then have no rows left, and no
+// proof of such a shape verifies. `o` has passed check_options, n is a power of two.
+inline int check_fri_shape(uint64_t n, const zkp_proof_options* o) {
+  if (n >> 56) return ZKP_ERR_TRACE_SHAPE;  // n * blowup_factor (<= 128) must not wrap
+  uint64_t fl = 1;
+  for (uint32_t l = fri_num_layers(n * o->blowup_factor, o); l; l--) {
+    fl *= o->fri_folding_factor;
+    if (fl > n) return ZKP_ERR_INVALID_OPTIONS;
+  }
+  return 0;
+}
+
 // Context::to_elements
 inline std::vector<felt> context_elements(const AirDesc& a, const zkp_proof_options* o) {
   std::vector<felt> e;

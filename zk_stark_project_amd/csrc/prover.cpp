@@ -29,6 +29,8 @@ int ProofRun::init(int air_id, const felt* d_trace_in, uint32_t width, uint64_t 
   logn = ilog2(n); logB = ilog2(B); logN = logn + logB;
   N = 1ull << logN;
   if (logN > MAX_LOG_DOMAIN || logn > MAX_LOG_TRACE) return ZKP_ERR_TRACE_SHAPE;
+  rc = check_fri_shape(n, o);  // the FRI layers fit the trace (before any device work)
+  if (rc) return rc;
   // coset sharding: rank r owns the LDE cosets [j0, j0 + Bl)
   R = (uint32_t)cm->world; rank = (uint32_t)cm->rank;
   if (R == 0 || (R & (R - 1)) || R > B || rank >= R) return ZKP_ERR_ARGUMENT;
@@ -426,11 +428,7 @@ FriCursor ProofRun::fri_layers() {
   // 7. FRI layers (FriProver::build_layers), folding factor 16. Layers stay
   // coset-sharded while each rank's Merkle range has >= 16 rows per coset,
   // then are all-gathered and finished identically on every rank.
-  L = 0;
-  {
-    uint64_t D = N, maxrem = (uint64_t)(o->fri_remainder_max_degree + 1) * B;
-    while (D > maxrem) { D /= F; L++; }
-  }
+  L = fri_num_layers(N, o);
   layers.assign(L + 1, FriLayer{});
   dres = ctx->buf<unsigned long long>("grind_res", 1);
   {

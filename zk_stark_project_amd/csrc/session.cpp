@@ -128,8 +128,9 @@ int zkp_session_create(zkp_ctx* ctx, zkp_air_id air_id, uint32_t width, uint64_t
     s->logn = ilog2(n); s->logB = ilog2(s->B); s->logN = s->logn + s->logB;
     s->N = n << s->logB;
     if (s->logN > MAX_LOG_DOMAIN || s->logn > MAX_LOG_TRACE) return (int)ZKP_ERR_TRACE_SHAPE;
-    uint64_t D = s->N, maxrem = (uint64_t)(o->fri_remainder_max_degree + 1) * s->B;
-    while (D > maxrem) { D /= s->F; s->L++; }
+    rc = check_fri_shape(n, o);
+    if (rc) return rc;
+    s->L = fri_num_layers(s->N, o);
     HIP_CHECK(hipSetDevice(ctx->device));
     if (!ctx->session_pool.empty()) {
       s->ctx = ctx->session_pool.back();
@@ -392,6 +393,8 @@ int zkp_channel_create(zkp_air_id air_id, uint32_t width, uint64_t n, const zkp_
     if (rc) return rc;
     if (n < 8 || (n & (n - 1)) || width == 0 || width > 255) return ZKP_ERR_TRACE_SHAPE;
     if (n_pub && !pub_elems) return ZKP_ERR_ARGUMENT;
+    rc = check_fri_shape(n, o);  // a channel only serves shapes the prover accepts
+    if (rc) return rc;
     std::vector<felt> pub(n_pub);
     for (uint64_t i = 0; i < n_pub; i++) pub[i] = make(pub_elems[i].lo, pub_elems[i].hi);
     AirDesc air;

@@ -237,17 +237,14 @@ int verify_impl(int air_id, const uint8_t* proof, uint64_t len, const zkp_felt* 
   const uint32_t logN = logn + ilog2(B);
   if (logN > 40) return ZKP_VERIFY_DESERIALIZATION;
   const uint64_t N = 1ull << logN;
+  if (check_fri_shape(n, &o) != 0) return ZKP_VERIFY_UNACCEPTABLE_OPTIONS;  // FRI layers past the trace
   std::vector<felt> pub(n_pub);
   for (uint64_t i = 0; i < n_pub; i++) pub[i] = make(pub_elems[i].lo, pub_elems[i].hi);
   AirDesc air;
   if (build_air(air, air_id, w, n, pub) != 0) return ZKP_VERIFY_PUB_INPUTS;
   if (num_constraints != air.num_t + air.a_col.size()) return ZKP_VERIFY_DESERIALIZATION;
   const uint32_t C = air.comp_cols();
-  uint32_t L = 0;
-  {
-    uint64_t D = N, maxrem = (uint64_t)(o.fri_remainder_max_degree + 1) * B;
-    while (D > maxrem) { D /= F; L++; }
-  }
+  const uint32_t L = fri_num_layers(N, &o);
   // ---- commitments, queries, OOD frame, FRI proof, nonce
   const uint64_t num_unique = r.uint(1);
   Reader com = r.section(2);
