@@ -68,13 +68,21 @@ enum { ZKP_FIELD_EXTENSION_NONE = 1 };
  *
  * Accepted: num_queries 1..255, blowup_factor a power of two in 2..128 and at
  * least the AIR's constraint-evaluation blowup, grinding_factor 0..32,
- * fri_folding_factor 16, fri_remainder_max_degree 2^k - 1 <= 255. The FRI layers
- * must also fit the trace: with L the number of layers (the domain n * blowup_factor
- * is divided by 16 while it exceeds (fri_remainder_max_degree + 1) * blowup_factor),
- * a trace of n rows needs n >= 16^L, so that the remainder has at least one
- * coefficient. Shapes past that (n = 64, blowup 8, remainder degree 0) have no
- * verifying proof: the prover, session and channel entries return
- * ZKP_ERR_INVALID_OPTIONS and zkp_verify ZKP_VERIFY_UNACCEPTABLE_OPTIONS. */
+ * fri_folding_factor F in {2, 4, 8, 16}, fri_remainder_max_degree 2^k - 1 <= 255.
+ * The FRI layers must also fit the trace: with L the number of layers (the domain
+ * n * blowup_factor is divided by F while it exceeds
+ * (fri_remainder_max_degree + 1) * blowup_factor), a trace of n rows needs
+ * n >= F^L, so that the remainder has at least one coefficient. Shapes past that
+ * (n = 64, blowup 8, remainder degree 0 at F = 16) have no verifying proof. A proof
+ * also has at most 16 FRI layers (zkp_transcript.fri_roots); F = 16 never gets past
+ * 7, F = 2 reaches 17 at n = 2^17, blowup 8, remainder degree 0. For both kinds of
+ * shape the prover, session and channel entries return ZKP_ERR_INVALID_OPTIONS and
+ * zkp_verify ZKP_VERIFY_UNACCEPTABLE_OPTIONS, decided on the host before any
+ * device work.
+ * Sharded proving (zkp_prove_sharded*) over more than one rank takes F = 16 only:
+ * every rank returns ZKP_ERR_INVALID_OPTIONS for another factor from its arguments
+ * alone, before the first collective, and the communicator stays usable. A
+ * communicator of one rank takes all four factors. */
 typedef struct zkp_proof_options {
   uint32_t num_queries;
   uint32_t blowup_factor;

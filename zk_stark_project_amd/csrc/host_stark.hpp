@@ -259,7 +259,8 @@ inline int check_options(const zkp_proof_options* o) {
   uint32_t b = o->blowup_factor;
   if (b < 2 || b > 128 || (b & (b - 1))) return ZKP_ERR_INVALID_OPTIONS;
   if (o->grinding_factor > 32) return ZKP_ERR_INVALID_OPTIONS;
-  if (o->fri_folding_factor != 16) return ZKP_ERR_INVALID_OPTIONS;  // the reference's value; only 16 is built
+  const uint32_t f = o->fri_folding_factor;  // winterfell's FriOptions: 2, 4, 8 or 16
+  if (f != 2 && f != 4 && f != 8 && f != 16) return ZKP_ERR_INVALID_OPTIONS;
   uint32_t r = o->fri_remainder_max_degree;
   if (r > 255 || ((r + 1) & r)) return ZKP_ERR_INVALID_OPTIONS;
   if (o->batching_constraints > 2 || o->batching_deep > 2) return ZKP_ERR_INVALID_OPTIONS;
@@ -278,11 +279,16 @@ inline uint32_t fri_num_layers(uint64_t N, const zkp_proof_options* o) {
 // holds at least blowup_factor points and the remainder has a coefficient. A
 // small fri_remainder_max_degree on a short trace breaks it (n = 64, B = 8,
 // r = 0: 512 -> 32 -> 2); the last layer would then have no rows left, and no
-// proof of such a shape verifies. `o` has passed check_options, n is a power of two.
+// proof of such a shape verifies. A proof also has at most FRI_MAX_LAYERS layers
+// (zkp_transcript.fri_roots and the device query gather hold that many; folding
+// factor 16 never gets past 7). `o` has passed check_options, n is a power of two.
+constexpr uint32_t FRI_MAX_LAYERS = 16;
 inline int check_fri_shape(uint64_t n, const zkp_proof_options* o) {
   if (n >> 56) return ZKP_ERR_TRACE_SHAPE;  // n * blowup_factor (<= 128) must not wrap
+  const uint32_t L = fri_num_layers(n * o->blowup_factor, o);
+  if (L > FRI_MAX_LAYERS) return ZKP_ERR_INVALID_OPTIONS;
   uint64_t fl = 1;
-  for (uint32_t l = fri_num_layers(n * o->blowup_factor, o); l; l--) {
+  for (uint32_t l = L; l; l--) {
     fl *= o->fri_folding_factor;
     if (fl > n) return ZKP_ERR_INVALID_OPTIONS;
   }

@@ -1,7 +1,7 @@
 // merkle.hip — CDNA4 (gfx950) kernels of the prover's hashing side: BLAKE3
 // leaf rows and Merkle trees (winter-crypto MerkleTree<Blake3_256>), the device
 // transcript (DefaultRandomCoin), grinding, query positions and openings, and
-// the FRI layers (fold-by-16, the fused small-layer tail, the remainder).
+// the FRI layers (fold by 2, 4, 8 or 16, the fused small-layer tail, the remainder).
 #include "kernels_dev.hpp"
 #include "blake3_quad.hpp"
 
@@ -183,7 +183,7 @@ __device__ __forceinline__ void merkle_leaf(const MerkleArgs& a, uint64_t i, uin
     b3::hash_felts([&](uint32_t c) { return base[c * cstride]; }, a.cols, d);
   } else if (MODE == 1) {
     // natural row i = j + B*t' -> coset j, positions t' + k*R
-    const felt* base = a.src + ((i & ((1ull << a.logB) - 1)) * 16) * a.R + (i >> a.logB);
+    const felt* base = a.src + ((i & ((1ull << a.logB) - 1)) * a.cols) * a.R + (i >> a.logB);
     b3::hash_felts([&](uint32_t k) { return base[k * a.R]; }, a.cols, d);
   } else if (MODE == 4 || MODE == 5) {  // MODE 0 with lazy GlobalUpdate columns (5: gu_row_shape)
     const uint64_t j = i & ((1ull << a.logB) - 1), t = i >> a.logB;
@@ -216,26 +216,30 @@ __device__ __forceinline__ void merge_quad(const uint32_t m[16], uint32_t q, uin
     compress_quad(m, q, b3::CHUNK_START | b3::CHUNK_END | b3::ROOT, o0, o1);
 }
 
-// Quad-cooperative digest of one FRI row of 16 felts (256 bytes: one chunk of
-// four blocks, hash_felts' nf <= 64 case); lane q returns words q and 4+q.
+// Quad-cooperative digest of one FRI row of F felts (16 * F bytes: one chunk of
+// F / 4 blocks, or one short block for F = 2; hash_felts' nf <= 64 case); lane q
+// returns words q and 4+q.
+template <int F = 16>
 __device__ __forceinline__ void fri_leaf_quad(const MerkleArgs& a, uint64_t i, uint32_t q, uint32_t& o0,
                                               uint32_t& o1) {
-  const felt* base = a.src + ((i & ((1ull << a.logB) - 1)) * 16) * a.R + (i >> a.logB);
+  constexpr uint32_t NB = F >= 4 ? F / 4 : 1, PER = F >= 4 ? 4 : F;  // blocks, felts per block
+  const felt* base = a.src + ((i & ((1ull << a.logB) - 1)) * F) * a.R + (i >> a.logB);
   o0 = sel4(q, b3::iv(0), b3::iv(1), b3::iv(2), b3::iv(3));
   o1 = sel4(q, b3::iv(4), b3::iv(5), b3::iv(6), b3::iv(7));
 #pragma unroll
-  for (uint32_t blk = 0; blk < 4; blk++) {
+  for (uint32_t blk = 0; blk < NB; blk++) {
     uint32_t m[16];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-      const felt v = base[(4 * blk + k) * a.R];
+      felt v = fp::zero();
+      if (k < (int)PER) v = base[(4 * blk + k) * a.R];
       m[4 * k + 0] = (uint32_t)v.lo;
       m[4 * k + 1] = (uint32_t)(v.lo >> 32);
       m[4 * k + 2] = (uint32_t)v.hi;
       m[4 * k + 3] = (uint32_t)(v.hi >> 32);
     }
-    const uint32_t fl = (blk == 0 ? b3::CHUNK_START : 0u) | (blk == 3 ? (b3::CHUNK_END | b3::ROOT) : 0u);
-    compress_quad(m, q, fl, o0, o1);
+    const uint32_t fl = (blk == 0 ? b3::CHUNK_START : 0u) | (blk == NB - 1 ? (b3::CHUNK_END | b3::ROOT) : 0u);
+    compress_quad(m, q, fl, o0, o1, 16 * PER);
   }
 }
 
@@ -1130,7 +1134,7 @@ __global__ __launch_bounds__(128) void k_gather_full(FullGatherArgs a, const uin
   } else {
     const uint32_t l = y - 1, logR = a.logrows[l];
     const uint64_t r = p & ((1ull << logR) - 1), m = a.m[l];
-    for (uint32_t e = t; e < 64; e += blockDim.x) {  // 16 values E[r + k*Rows] (coset-major)
+    for (uint32_t e = t; e < 4 * a.F; e += blockDim.x) {  // F values E[r + k*Rows] (coset-major)
       const uint64_t idx = r + ((uint64_t)(e >> 2) << logR);
       const uint64_t j = idx & (B - 1), tt = idx >> a.logB;
       rec[e] = reinterpret_cast<const uint32_t*>(a.E[l] + j * m + tt)[e & 3];
@@ -1138,7 +1142,7 @@ __global__ __launch_bounds__(128) void k_gather_full(FullGatherArgs a, const uin
     for (uint32_t e = t; e < logR * 8; e += blockDim.x) {
       const uint32_t d = e / 8, wd = e & 7;
       const uint64_t node = (((1ull << logR) + r) >> d) ^ 1ull;
-      rec[64 + e] = a.fnodes[l][node * 8 + wd];
+      rec[4 * a.F + e] = a.fnodes[l][node * 8 + wd];
     }
   }
 }
@@ -1211,7 +1215,43 @@ __device__ __forceinline__ felt fri_fold_row(const felt* __restrict__ E, uint64_
   return mul(acc, eps_inv[8]);
 }
 
-// The same fold by a quad of lanes (the latency-bound small layers: one row's
+// fold-by-F for F = 2, 4, 8 (same layout, F values per row at positions t' + k*mF
+// of coset jl, mF = m / F): the row's degree-< F polynomial through (x_r w_F^k, v_k)
+// at alpha, as u = iDFT_F(row) (unscaled) and (1/F) sum_k u_k beta^k. w_F^-i is
+// eps_inv[i * 16 / F]; 1/8, 1/4, 1/2 follow 1/16 at eps_inv[9..12). F = 2 has no
+// twiddle: (v0 + v1)/2 + beta (v0 - v1)/2.
+template <int F>
+__device__ __forceinline__ felt fri_fold_row_f(const felt* __restrict__ E, uint64_t q, uint32_t logmF, uint32_t j0,
+                                               uint32_t logB, const felt* alpha_p, felt off_inv,
+                                               const felt* __restrict__ itw_lev, const felt* __restrict__ eps_inv) {
+  static_assert(F == 2 || F == 4 || F == 8, "fold-16 has its own functions");
+  constexpr int LOGF = F == 2 ? 1 : (F == 4 ? 2 : 3);
+  const uint64_t mF = 1ull << logmF;
+  const uint64_t jl = q >> logmF, tp = q & (mF - 1);
+  const uint64_t r = (j0 + jl) + (tp << logB);
+  const felt* src = E + ((jl * F) << logmF) + tp;
+  felt v[F];
+#pragma unroll
+  for (int k = 0; k < F; k++) v[k] = src[k * mF];
+  const felt beta = mul(*alpha_p, mul(off_inv, itw_lev[r]));
+  // Gentleman-Sande, natural in -> bit-reversed out (compile-time indices: the row stays in registers)
+  static_for<0, LOGF>([&](auto st) {
+    constexpr int span = F >> (decltype(st)::value + 1);
+    static_for<0, F / 2>([&](auto bf) {
+      constexpr int i = decltype(bf)::value % span, lo = (decltype(bf)::value / span) * 2 * span + i;
+      const felt x = v[lo], y = v[lo + span];
+      v[lo] = add(x, y);
+      if constexpr (i == 0) v[lo + span] = sub(x, y);
+      else v[lo + span] = mul(sub(x, y), eps_inv[i * (8 / span)]);
+    });
+  });
+  // Horner over k = F-1..0 with u_k = v[rev(k)]
+  felt acc = v[kc::rev_const(F - 1, LOGF)];
+  static_for<1, F>([&](auto kk) { acc = add(mul(acc, beta), v[kc::rev_const(F - 1 - decltype(kk)::value, LOGF)]); });
+  return mul(acc, eps_inv[12 - LOGF]);
+}
+
+// The fold-16 by a quad of lanes (the latency-bound small layers: one row's
 // 35 serial products become 19). Lane qd holds v[qd + 4i], i < 4: the iDFT's
 // span-8 and span-4 stages stay in the lane, the span-2 and span-1 stages pair
 // lanes qd^2 and qd^1 (DPP). Lane qd then holds u_k for k = 4*rev2(qd) + rev2(i),
@@ -1311,11 +1351,23 @@ __global__ __launch_bounds__(TPB) void k_fri_fold16(const felt* __restrict__ E, 
   out[q] = fri_fold_row(E, q, logm16, j0, logB, alpha_p, off_inv, itw_lev, eps_inv);
 }
 
+template <int F>
+__global__ __launch_bounds__(TPB) void k_fri_fold(const felt* __restrict__ E, uint64_t rows, uint32_t logmF,
+                                                  uint32_t j0, uint32_t logB, const felt* __restrict__ alpha_p,
+                                                  felt off_inv, const felt* __restrict__ itw_lev,
+                                                  const felt* __restrict__ eps_inv, felt* __restrict__ out) {
+  const uint64_t q = blockIdx.x * (uint64_t)TPB + threadIdx.x;
+  if (q >= rows) return;
+  out[q] = fri_fold_row_f<F>(E, q, logmF, j0, logB, alpha_p, off_inv, itw_lev, eps_inv);
+}
+
 // The FRI tail in one 512-thread block (world 1): for each layer of <= 128
 // rows, quad-hashed leaves -> tree (quad merges, levels in LDS, every node
 // written) -> coin step (alpha, root) -> fold into the next layer; then the
 // remainder (as k_fri_remainder). Replaces 2 launches per small layer + the
 // remainder launch, each of which costs its ~15-25 us launch/latency floor.
+// F < 16: the rows are short, so a lane folds a whole row (fri_fold_row_f).
+template <int F>
 __global__ __launch_bounds__(512) void k_fri_tail(FriTailArgs a) {
   __shared__ uint32_t sd[128 * 9];
   __shared__ felt s_c[256];
@@ -1329,10 +1381,10 @@ __global__ __launch_bounds__(512) void k_fri_tail(FriTailArgs a) {
     ma.src = y.E;
     ma.R = 1ull << y.logm16;
     ma.logB = a.logB;
-    ma.cols = 16;
+    ma.cols = F;
     if (nd < R) {  // whole quads
       uint32_t o0, o1;
-      fri_leaf_quad(ma, nd, q, o0, o1);
+      fri_leaf_quad<F>(ma, nd, q, o0, o1);
       sd[nd * 9 + q] = o0;
       sd[nd * 9 + 4 + q] = o1;
       uint32_t* dst = y.nodes + (uint64_t)(R + nd) * 8;
@@ -1366,10 +1418,12 @@ __global__ __launch_bounds__(512) void k_fri_tail(FriTailArgs a) {
     }
     __threadfence();  // alpha (and this layer's fold output below) visible block-wide
     __syncthreads();
-    {  // one quad per row (R <= 128 rows, 128 quads): whole quads active, rows clamped
+    if constexpr (F == 16) {  // one quad per row (R <= 128 rows, 128 quads): whole quads active, rows clamped
       const felt fv = fri_fold_row_quad(y.E, nd < R ? nd : R - 1, q, y.logm16, 0, a.logB, y.alpha_out, y.off_inv,
                                         y.lev, a.eps_inv);
       if (nd < R && q == 0) y.out[nd] = fv;
+    } else {
+      if (t < R) y.out[t] = fri_fold_row_f<F>(y.E, t, y.logm16, 0, a.logB, y.alpha_out, y.off_inv, y.lev, a.eps_inv);
     }
     __threadfence();
     __syncthreads();
@@ -1600,11 +1654,21 @@ void launch_coin_fri_layer(Prof& prof, hipStream_t s, uint32_t* seed, const uint
 void launch_fri_fold(Prof& prof, hipStream_t s, const felt* E, uint64_t m16, uint32_t Bl, uint32_t j0,
                      uint32_t logB, uint32_t F, const felt* alpha, felt off_inv, const felt* itw, uint32_t logD,
                      const felt* eps_inv, felt* out) {
-  (void)F;  // only 16 is compiled (the reference's fri_folding_factor)
   const felt* lev = itw + ((1ull << (logD - 1)) - 1);  // w_D^-r, r < D/2
   uint32_t logm16 = 0;
   while ((1ull << logm16) < m16) logm16++;
   const uint64_t rows = m16 * Bl;
+  if (F != 16) {  // m16 = m / F here: one lane per row at every size (rows of 2, 4, 8 are too short to share)
+#define ZKP_FOLD(FF)                                                                                             \
+  case FF:                                                                                                       \
+    LAUNCH(prof, "fri_fold" #FF, s, (double)rows * (FF * 16.0 + 16.0),                                           \
+           hipLaunchKernelGGL(k_fri_fold<FF>, dim3(blocks_for(rows)), dim3(TPB), 0, s, E, rows, logm16, j0, logB, \
+                              alpha, off_inv, lev, eps_inv, out));                                               \
+    return;
+    switch (F) { ZKP_FOLD(2) ZKP_FOLD(4) ZKP_FOLD(8) }
+#undef ZKP_FOLD
+    launch_fail(ZKP_ERR_DEVICE, "internal: FRI folding factor");
+  }
   // up to 2^15 rows the layer is latency-bound (under one wave per SIMD): a quad
   // per row shortens the chain; above that the one-lane form issues fewer products
   if (rows <= (1ull << 15)) {
@@ -1620,10 +1684,19 @@ void launch_fri_fold(Prof& prof, hipStream_t s, const felt* E, uint64_t m16, uin
 
 void launch_fri_tail(Prof& prof, hipStream_t s, const FriTailArgs& a) {
   if (a.nl > FRI_TAIL_MAX || (a.rem_m << a.logB) > 256) launch_fail(ZKP_ERR_DEVICE, "internal: FRI tail shape");
-  for (uint32_t l = 0; l < a.nl; l++)
-    if (a.ly[l].logm16 + a.logB > 7)  // <= 128 rows: one quad per row in 512 threads
+  for (uint32_t l = 0; l < a.nl; l++) {
+    const uint32_t logrows = a.ly[l].logm16 + a.logB;
+    if (logrows > 7)  // <= 128 rows: one quad per row in 512 threads
       launch_fail(ZKP_ERR_DEVICE, "internal: FRI tail layer over 128 rows");
-  LAUNCH(prof, "fri_tail", s, 0.0, hipLaunchKernelGGL(k_fri_tail, dim3(1), dim3(512), 0, s, a));
+    if (logrows < 1) launch_fail(ZKP_ERR_DEVICE, "internal: FRI tail layer of one row");
+  }
+  switch (a.F) {
+    case 2: LAUNCH(prof, "fri_tail", s, 0.0, hipLaunchKernelGGL(k_fri_tail<2>, dim3(1), dim3(512), 0, s, a)); break;
+    case 4: LAUNCH(prof, "fri_tail", s, 0.0, hipLaunchKernelGGL(k_fri_tail<4>, dim3(1), dim3(512), 0, s, a)); break;
+    case 8: LAUNCH(prof, "fri_tail", s, 0.0, hipLaunchKernelGGL(k_fri_tail<8>, dim3(1), dim3(512), 0, s, a)); break;
+    case 16: LAUNCH(prof, "fri_tail", s, 0.0, hipLaunchKernelGGL(k_fri_tail<16>, dim3(1), dim3(512), 0, s, a)); break;
+    default: launch_fail(ZKP_ERR_DEVICE, "internal: FRI folding factor");
+  }
 }
 
 void launch_leaf_hash_shard(Prof& prof, hipStream_t s, int mode, const felt* src, uint64_t n, uint32_t cols,

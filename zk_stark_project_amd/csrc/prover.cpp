@@ -425,7 +425,7 @@ void ProofRun::fri_stage() {
 // the layer loop on the device: trees, coin steps, folds; then the remainder,
 // the first grinding chunk and (world 1) the query tail
 FriCursor ProofRun::fri_layers() {
-  // 7. FRI layers (FriProver::build_layers), folding factor 16. Layers stay
+  // 7. FRI layers (FriProver::build_layers), folding factor F. Layers stay
   // coset-sharded while each rank's Merkle range has >= 16 rows per coset,
   // then are all-gathered and finished identically on every rank.
   L = fri_num_layers(N, o);
@@ -459,8 +459,9 @@ FriCursor ProofRun::fri_layers() {
     // world 1 with a device remainder: the layers of <= 128 rows, their coin
     // steps and the remainder run as one single-block launch (k_fri_tail)
     static const bool no_fri_tail = getenv("ZKP_NO_FRI_TAIL") != nullptr;  // A/B switch
-    const bool fuse_tail = R == 1 && o->grinding_factor > 0 && F == 16 && (N >> (4 * L)) <= 256 && !no_fri_tail;
+    const bool fuse_tail = R == 1 && o->grinding_factor > 0 && (N >> (ilog2(F) * L)) <= 256 && !no_fri_tail;
     FriTailArgs fta{};
+    fta.F = F;
     for (uint32_t l = 0; l < L; l++) {
       const uint64_t m16 = m / F;
       if (sh && (m16 >> logR) < 16) replicate(l);
@@ -550,7 +551,7 @@ FriCursor ProofRun::fri_layers() {
       dpos = ctx->buf<uint64_t>("query_pos", o->num_queries);
       launch_query_positions(pf, st, coin_d, dres, o->num_queries, N, dpos);
       ga.tlde = tlde; ga.clde = clde; ga.tnodes = ttree.nodes; ga.cnodes = ctree.nodes;
-      ga.n = n; ga.w = w; ga.C = C; ga.logB = logB; ga.logN = logN; ga.nlayers = L;
+      ga.n = n; ga.w = w; ga.C = C; ga.logB = logB; ga.logN = logN; ga.nlayers = L; ga.F = F;
       uint64_t off_w = 0;
       ga.seg_off[0] = 0;
       ga.rec_words[0] = 4 * (w + C) + 16 * logN;
@@ -561,7 +562,7 @@ FriCursor ProofRun::fri_layers() {
         ga.m[l] = layers[l].m;
         ga.logrows[l] = logB + ilog2(layers[l].m / F);
         ga.seg_off[1 + l] = off_w;
-        ga.rec_words[1 + l] = 64 + 8 * ga.logrows[l];
+        ga.rec_words[1 + l] = 4 * F + 8 * ga.logrows[l];
         off_w += (uint64_t)o->num_queries * ga.rec_words[1 + l];
       }
       full_h.resize(off_w);

@@ -224,11 +224,22 @@ void ProofRun::composition_gather_lde(felt* slice, bool derive, uint64_t nR, uin
 
 }  // namespace zkpi
 
+namespace {
+// Sharded FRI layers (their leaf pass, the replication threshold) are built for 16
+// values per row: a group of more than one rank refuses every other folding factor.
+// The answer depends on the arguments alone, so every rank returns it before its
+// first collective and none can block: the communicator is not aborted and stays usable.
+bool sharded_factor_refused(const zkp_comm* comm, const zkp_proof_options* o) {
+  return comm && o && comm->world > 1 && check_options(o) == 0 && o->fri_folding_factor != 16;
+}
+}  // namespace
+
 extern "C" {
 
 int zkp_prove_sharded(zkp_ctx* ctx, zkp_comm* comm, zkp_air_id air, const zkp_felt* trace, uint32_t width,
                       uint64_t n, const zkp_felt* pub, uint64_t n_pub, const zkp_proof_options* opts, uint8_t** proof,
                       uint64_t* proof_len, zkp_transcript* transcript) {
+  if (ctx && sharded_factor_refused(comm, opts)) return ZKP_ERR_INVALID_OPTIONS;
   int rc = guarded(ctx, [&] {
     ctx->err.clear();
     HIP_CHECK(hipSetDevice(ctx->device));
@@ -245,6 +256,7 @@ int zkp_prove_sharded(zkp_ctx* ctx, zkp_comm* comm, zkp_air_id air, const zkp_fe
 int zkp_prove_sharded_device(zkp_ctx* ctx, zkp_comm* comm, zkp_air_id air, const void* d_trace, uint32_t width,
                              uint64_t n, const zkp_felt* pub, uint64_t n_pub, const zkp_proof_options* opts,
                              uint8_t** proof, uint64_t* proof_len, zkp_transcript* transcript) {
+  if (ctx && sharded_factor_refused(comm, opts)) return ZKP_ERR_INVALID_OPTIONS;
   int rc = guarded(ctx, [&] {
     ctx->err.clear();
     HIP_CHECK(hipSetDevice(ctx->device));

@@ -9,8 +9,8 @@ using namespace zkpi;
 namespace zkpi {
 
 // commit the rows of a coset-major source held by this rank (cosets [j0, j0+Bl)):
-// mode 0 = LDE rows (cols columns, n rows per coset), mode 1 = FRI rows (16
-// values, 2^logrows rows per coset). Unsharded sources hold all B cosets.
+// mode 0 = LDE rows (cols columns, n rows per coset), mode 1 = FRI rows (cols =
+// folding factor values, 2^logrows rows per coset). Unsharded sources hold all B cosets.
 // Unsharded trees finish in the last block of their top launch (MerkleTail);
 // sharded trees in k_shard_top over the all-gathered subtree roots. With coin
 // (coefficients, z or a FRI layer's alpha) that block also runs the coin step,
@@ -30,7 +30,7 @@ bool commit_rows(zkp_ctx* ctx, zkp_comm* cm, int mode, const felt* src, uint64_t
     MerkleTail tail = coin ? *coin : MerkleTail{};
     tail.done = done;
     bool ran = mode == 0 ? launch_merkle_lde(pf, st, src, cols, logB, n, tr.nodes, L, &tail, lc, gl)
-                         : launch_merkle_fri(pf, st, src, 1ull << logrows, logB, 16, tr.nodes, &tail);
+                         : launch_merkle_fri(pf, st, src, 1ull << logrows, logB, cols, tr.nodes, &tail);
     tr.top.assign(2, {});
     if (fetch_root) {  // otherwise the caller reads nodes[1] later
       ctx->download(root, tr.nodes + 8, 32);
@@ -534,21 +534,22 @@ void openings_from_full(const std::vector<uint64_t>& raw, const std::vector<uint
       const uint32_t* rec = full + ga.seg_off[1 + l] + (uint64_t)i * ga.rec_words[1 + l];
       for (uint32_t k = 0; k < F; k++) put(rec + 4 * k, 4);
     }
-    paths(op.bf[l], lv, 1 + l, 64);
+    paths(op.bf[l], lv, 1 + l, 4 * F);
     cur = fp;
   }
 }
 
-// constants of the fold-16 iDFT (w_16^-m for m < 8, then 16^-1), cached per context
+// constants of the fold iDFTs, cached per context: w_16^-m for m < 8 (w_8^-m and
+// w_4^-m by stride), then 1/16, 1/8, 1/4, 1/2
 const felt* fold_constants(zkp_ctx* ctx) {
-  felt* deps = ctx->buf<felt>("eps_inv", 9);
+  felt* deps = ctx->buf<felt>("eps_inv", 12);
   if (!ctx->have_cached("eps_inv")) {
-    std::vector<felt> eps(9);
+    std::vector<felt> eps(12);
     felt einv = inv(root_of_unity(4));
     eps[0] = one();
     for (int m = 1; m < 8; m++) eps[m] = mul(eps[m - 1], einv);
-    eps[8] = inv(felt_u64(16));
-    ctx->upload(deps, eps.data(), 9 * 16);
+    for (int k = 0; k < 4; k++) eps[8 + k] = inv(felt_u64(16 >> k));
+    ctx->upload(deps, eps.data(), eps.size() * 16);
   }
   return deps;
 }

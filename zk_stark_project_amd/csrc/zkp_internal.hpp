@@ -126,7 +126,7 @@ struct GuLazy {
 bool launch_merkle_lde(Prof& prof, hipStream_t s, const felt* lde, uint32_t cols, uint32_t logB, uint64_t n,
                        uint32_t* nodes, uint64_t L, const MerkleTail* tail = nullptr, const LastCol* lc = nullptr,
                        const GuLazy* gl = nullptr);
-// FRI layer tree over coset-major evaluations (B cosets of 16*m16): leaf r = j + B*t'
+// FRI layer tree over coset-major evaluations (B cosets of F*m16, m16 = m / F rows each): leaf r = j + B*t'
 bool launch_merkle_fri(Prof& prof, hipStream_t s, const felt* E, uint64_t m16, uint32_t logB, uint32_t F,
                        uint32_t* nodes, const MerkleTail* tail = nullptr);
 // nodes[1..L) from leaf digests already in nodes[L..2L)
@@ -177,6 +177,7 @@ struct FullGatherArgs {
   const uint32_t* cnodes;
   uint64_t n;
   uint32_t w, C, logB, logN, nlayers;
+  uint32_t F;                               // values per FRI row (the folding factor)
   const felt* E[GATHER_MAX_LAYERS];         // FRI layer l evaluations, coset-major (m[l] per coset)
   const uint32_t* fnodes[GATHER_MAX_LAYERS];
   uint64_t m[GATHER_MAX_LAYERS];
@@ -185,7 +186,7 @@ struct FullGatherArgs {
   uint32_t rec_words[GATHER_MAX_LAYERS + 1];
 };
 // record of raw position i in segment 0: [w + C row felts | trace path | constraint path]
-// (logN sibling digests each, leaf level first); segment 1 + l: [16 felts | logrows[l] digests]
+// (logN sibling digests each, leaf level first); segment 1 + l: [F felts | logrows[l] digests]
 void launch_gather_full(Prof& prof, hipStream_t s, const FullGatherArgs& a, uint32_t q, const uint64_t* pos,
                         uint32_t* out);
 
@@ -349,18 +350,19 @@ void launch_deep_lincomb(Prof& prof, hipStream_t s, const felt* coef, uint32_t w
                          uint64_t np, const felt* gamma, felt* out,  // positions [p0, p0 + np) -> out[0, np)
                          felt* scratch);  // column-group partials (np per group, see lincomb_groups), nullable
 
-// FRI fold-by-F (F = 16) over coset-major evaluations of the cosets [j0, j0+Bl)
-// (16*m16 positions each): natural row r = j + B*t', x_r = off * w_D^r; alpha read from device
+// FRI fold-by-F (F = 2, 4, 8, 16) over coset-major evaluations of the cosets [j0, j0+Bl)
+// (F*m16 positions each, m16 = m / F): natural row r = j + B*t', x_r = off * w_D^r; alpha
+// read from device; eps_inv_dev = fold_constants
 void launch_fri_fold(Prof& prof, hipStream_t s, const felt* E, uint64_t m16, uint32_t Bl, uint32_t j0,
                      uint32_t logB, uint32_t F, const felt* alpha, felt off_inv, const felt* itw, uint32_t logD,
                      const felt* eps_inv_dev, felt* out);
 // the FRI tail in one block (world 1): layers of <= 128 rows (tree, coin step,
-// fold) and the remainder, in order
-constexpr uint32_t FRI_TAIL_MAX = 4;
+// fold) and the remainder, in order. Folding by 2 has up to 7 such layers (128 .. 2 rows).
+constexpr uint32_t FRI_TAIL_MAX = 7;
 struct FriTailLayer {
-  const felt* E;        // layer evaluations, coset-major (B cosets of 16 * 2^logm16)
+  const felt* E;        // layer evaluations, coset-major (B cosets of F * 2^logm16)
   uint32_t* nodes;      // the layer's tree (16 * rows words)
-  uint32_t logm16;
+  uint32_t logm16;      // log2 of the rows per coset (m / F)
   felt off_inv;
   const felt* lev;      // w_D^-r table of the layer's domain
   felt* out;            // folded evaluations (the next layer)
@@ -368,7 +370,7 @@ struct FriTailLayer {
   uint32_t* root_out;
 };
 struct FriTailArgs {
-  uint32_t nl, logB;
+  uint32_t nl, logB, F;
   FriTailLayer ly[FRI_TAIL_MAX];
   uint32_t* coin_seed;
   const felt* eps_inv;
