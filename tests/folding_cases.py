@@ -40,6 +40,10 @@ DEPTH_CASES = [
 # b. layer 0 with more than 2^16 rows (the lane-subtree leaf pass), MiMC B 8 r 7: (F, n, L)
 WIDE_LAYER_CASES = [(2, 1 << 15, 12), (4, 1 << 16, 7), (8, 1 << 17, 5)]
 
+# F = 16 with a first layer above 2^15 rows, MiMC B 8 r 7: (n, L). Layer 0 (2^16 rows) is
+# folded one lane per row (k_fri_fold<16>), layer 1 (2^12 rows) one quad per row
+FOLD16_LANE_CASE = (1 << 17, 4)
+
 # shapes refused on the host, MiMC (F, n, B, r): F^L > n, and L > 16
 PAST_TRACE = (8, 256, 8, 0)
 TOO_DEEP = (2, 1 << 17, 8, 0)

@@ -4,7 +4,8 @@ The factor selects device code of its own: the fold kernels (k_fri_fold<F>,
 csrc/merkle.hip), rows of 2, 4 and 8 values in the layer trees (one or two BLAKE3
 blocks; the LDS-fused tree up to 2^16 rows, the lane-subtree pass above), trees of
 2 and 4 leaves, up to 16 layers, the fused tail (k_fri_tail<F>) with up to 7 small
-layers, and 4 * F words per row in the device query gather.
+layers, and 4 * F words per row in the device query gather. One F = 16 case sits with
+them (b.): k_fri_fold<16> above 2^15 rows, which the fast F = 16 tests do not reach.
 
 Every proving case asserts what check_proof of test_gpu_options.py asserts: GPU
 bytes == oracle bytes, equal trace root, constraint root and nonce, the listed
@@ -16,8 +17,8 @@ import numpy as np
 import pytest
 
 import oracle_ref as O
-from folding_cases import (DEPTH_CASES, FACTORS, MAX_FRI_LAYERS, PAST_TRACE, TOO_DEEP, WIDE_LAYER_CASES, fri_layers,
-                           options)
+from folding_cases import (DEPTH_CASES, FACTORS, FOLD16_LANE_CASE, MAX_FRI_LAYERS, PAST_TRACE, TOO_DEEP,
+                           WIDE_LAYER_CASES, fri_layers, options)
 from proof_format import sections
 from test_gpu_options import check_proof, gu_inputs, mimc_inputs, tu_inputs
 from test_gpu_stages import check_by_stages
@@ -48,6 +49,15 @@ def test_first_layer_above_65536_rows(ctx, fold, n, layers):
     """The smallest n whose first layer has more than 2^16 rows (N / F = 2^17)."""
     assert n * 8 // fold == 1 << 17
     check_proof(ctx, mimc_inputs(n), options(20, 8, 4, 7, fold), layers=layers)
+
+
+def test_fold16_above_32768_rows(ctx):
+    """F = 16 at the smallest n whose first layer (N / 16 = 2^16 rows) is past the quad
+    fold's 2^15 rows, so k_fri_fold<16> folds it; the next layer (2^12 rows) takes the
+    quad fold. Only slow tests reached the one-lane fold-16 before."""
+    n, layers = FOLD16_LANE_CASE
+    assert n * 8 // 16 == 1 << 16 and n * 8 // 16 ** 2 == 1 << 12
+    check_proof(ctx, mimc_inputs(n), options(20, 8, 4, 7, 16), layers=layers)
 
 
 # ---------------------------------------------------------------- c. wide AIRs, tiny trees

@@ -89,38 +89,27 @@ ZKP_HD void set_iv(uint32_t cv[8]) {
   for (int i = 0; i < 8; i++) cv[i] = iv(i);
 }
 
-// compress() or its rolled form (ROLLED: latency-bound call sites, see compress_r)
-template <bool ROLLED>
-ZKP_HD void compress_t(uint32_t cv[8], const uint32_t m[16], uint64_t counter, uint32_t block_len, uint32_t flags) {
-  if constexpr (ROLLED)
-    compress_r(cv, m, counter, block_len, flags);
-  else
-    compress(cv, m, counter, block_len, flags);
-}
-
 // merge(a, b) = BLAKE3(a || b): one 64-byte block, single chunk, root
-template <bool ROLLED = false>
 ZKP_HD void merge(const uint32_t a[8], const uint32_t b[8], uint32_t out[8]) {
   uint32_t m[16];
   for (int i = 0; i < 8; i++) { m[i] = a[i]; m[8 + i] = b[i]; }
   set_iv(out);
-  compress_t<ROLLED>(out, m, 0, 64, CHUNK_START | CHUNK_END | ROOT);
+  compress(out, m, 0, 64, CHUNK_START | CHUNK_END | ROOT);
 }
 
 // parent node of the BLAKE3 chunk tree
-template <bool ROLLED = false>
 ZKP_HD void parent(const uint32_t l[8], const uint32_t r[8], bool root, uint32_t out[8]) {
   uint32_t m[16];
   for (int i = 0; i < 8; i++) { m[i] = l[i]; m[8 + i] = r[i]; }
   set_iv(out);
-  compress_t<ROLLED>(out, m, 0, 64, PARENT | (root ? ROOT : 0u));
+  compress(out, m, 0, 64, PARENT | (root ? ROOT : 0u));
 }
 
 // chaining value of chunk `ci` covering felts [f0, f1) (at most 64 felts = 1024 bytes)
 // The next block's felts are fetched before the current block is compressed
 // (a register double buffer), so a row read from HBM overlaps its hashing
 // instead of waiting once per 64-byte block.
-template <bool ROLLED = false, typename Get>
+template <typename Get>
 ZKP_HD void hash_chunk(Get get, uint32_t f0, uint32_t f1, uint64_t ci, bool root, uint32_t cv[8]) {
   set_iv(cv);
   uint32_t nblocks = f1 > f0 ? (f1 - f0 + 3) / 4 : 1;
@@ -143,7 +132,7 @@ ZKP_HD void hash_chunk(Get get, uint32_t f0, uint32_t f1, uint64_t ci, bool root
     const uint32_t cnt = f1 - base < 4 ? f1 - base : 4;  // (nblocks = 1 with f1 == f0: cnt = 0)
     uint32_t fl = (b == 0 ? CHUNK_START : 0u) | (b == nblocks - 1 ? CHUNK_END : 0u);
     if (root && b == nblocks - 1) fl |= ROOT;
-    compress_t<ROLLED>(cv, m, ci, 16 * (f1 > f0 ? cnt : 0u), fl);
+    compress(cv, m, ci, 16 * (f1 > f0 ? cnt : 0u), fl);
 #pragma unroll
     for (int k = 0; k < 4; k++) cur[k] = nxt[k];
   }

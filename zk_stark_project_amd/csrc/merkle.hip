@@ -13,59 +13,6 @@ using kc::static_for;
 namespace {
 
 // ------------------------------------------------------------------ hashing
-__global__ __launch_bounds__(TPB) void k_leaf_hash_lde(const felt* __restrict__ lde, uint32_t cols, uint32_t logB,
-                                                       uint64_t n, uint32_t* __restrict__ nodes, uint64_t L) {
-  uint64_t i = blockIdx.x * (uint64_t)TPB + threadIdx.x;
-  if (i >= L) return;
-  uint64_t j = i & ((1ull << logB) - 1), t = i >> logB;
-  const felt* base = lde + j * n + t;
-  const uint64_t cstride = n << logB;
-  uint32_t d[8];
-  b3::hash_felts([&](uint32_t c) { return base[c * cstride]; }, cols, d);
-  store_digest(nodes + (L + i) * 8, d);
-}
-
-__global__ __launch_bounds__(TPB) void k_leaf_hash_fri(const felt* __restrict__ E, uint64_t R, uint32_t F,
-                                                       uint32_t* __restrict__ nodes) {
-  uint64_t r = blockIdx.x * (uint64_t)TPB + threadIdx.x;
-  if (r >= R) return;
-  uint32_t d[8];
-  b3::hash_felts([&](uint32_t k) { return E[r + k * R]; }, F, d);
-  store_digest(nodes + (R + r) * 8, d);
-}
-
-// nodes[s + i] = merge(nodes[2(s+i)], nodes[2(s+i)+1]) for i < s
-__global__ __launch_bounds__(TPB) void k_merkle_level(uint32_t* nodes, uint64_t s) {
-  uint64_t i = blockIdx.x * (uint64_t)TPB + threadIdx.x;
-  if (i >= s) return;
-  uint64_t node = s + i;
-  uint32_t m[16];
-  load_digest(nodes + 2 * node * 8, m);
-  load_digest(nodes + (2 * node + 1) * 8, m + 8);
-  uint32_t out[8];
-  b3::set_iv(out);
-  b3::compress(out, m, 0, 64, b3::CHUNK_START | b3::CHUNK_END | b3::ROOT);
-  store_digest(nodes + node * 8, out);
-}
-
-// remaining top levels (s_start .. 1) inside one workgroup
-__global__ __launch_bounds__(1024) void k_merkle_top(uint32_t* nodes, uint64_t s_start) {
-  for (uint64_t s = s_start; s >= 1; s >>= 1) {
-    for (uint64_t i = threadIdx.x; i < s; i += blockDim.x) {
-      uint64_t node = s + i;
-      uint32_t m[16];
-      load_digest(nodes + 2 * node * 8, m);
-      load_digest(nodes + (2 * node + 1) * 8, m + 8);
-      uint32_t out[8];
-      b3::set_iv(out);
-      b3::compress(out, m, 0, 64, b3::CHUNK_START | b3::CHUNK_END | b3::ROOT);
-      store_digest(nodes + node * 8, out);
-    }
-    __threadfence_block();
-    __syncthreads();
-  }
-}
-
 // Fused Merkle build: each block turns up to 512 consecutive leaves into all
 // 9 levels of their subtree (leaf digests -> subtree root) with the levels
 // held in LDS and every node written once to nodes[] (tree layout: level d of
@@ -174,28 +121,61 @@ __device__ __forceinline__ felt derive_last(const felt* v, felt h, felt kappa, f
   return mul(sub(h, acc), kinv);
 }
 
+// ---- row digests, by the row's base pointer and the stride between its felts (shared by
+// the tree builders' merkle_leaf and the sharded leaf pass k_leaf_hash_shard)
+// an LDE row (stride = the LDE's column stride) or a FRI row (stride = rows per coset)
+__device__ __forceinline__ void row_digest(const felt* base, uint64_t stride, uint32_t cols, uint32_t d[8]) {
+  b3::hash_felts([&](uint32_t c) { return base[c * stride]; }, cols, d);
+}
+
+// an LDE row with lazy GlobalUpdate columns (MODE 4; MODE 5: of gu_row_shape): prev = the
+// previous row of its coset, l = L_0 at the row
+template <int MODE>
+__device__ __forceinline__ void gu_row_digest(const GuLazy& gl, const felt* base, const felt* prev, uint64_t cstride,
+                                              felt l, uint32_t cols, uint32_t d[8]) {
+  if constexpr (MODE == 5)
+    gu_row_hash(gl, base, prev, cstride, l, d);
+  else
+    b3::hash_felts([&](uint32_t c) { return c < gl.wi ? base[c * cstride] : gu_lazy_value(gl, base, prev, cstride, l, c); },
+                   cols, d);
+}
+
+// a narrow LDE row (COLS <= 8) held in registers, so that a caller can load several rows
+// before it hashes any: narrow_row_load reads the stored columns (DERIVE: all but the
+// last, and the row's constraint evaluation h = lc.H[off], off = the row's offset in its
+// column); narrow_row_digest derives column COLS-1 from h and coset j's kappa, writes it
+// to lc.out[off] (DERIVE), and hashes the row
+template <int COLS, bool DERIVE>
+__device__ __forceinline__ void narrow_row_load(const felt* base, uint64_t cstride, const LastCol& lc, uint64_t off,
+                                                felt v[COLS], felt& h) {
+  constexpr int RD = DERIVE ? COLS - 1 : COLS;  // columns read from the source
+#pragma unroll
+  for (int c = 0; c < RD; c++) v[c] = base[c * cstride];
+  h = DERIVE ? lc.H[off] : fp::zero();
+}
+template <int COLS, bool DERIVE>
+__device__ __forceinline__ void narrow_row_digest(felt v[COLS], felt h, const LastCol& lc, uint64_t j, uint64_t off,
+                                                  uint32_t d[8]) {
+  if constexpr (DERIVE) {
+    v[COLS - 1] = derive_last<COLS>(v, h, lc.kap[2 * j], lc.kap[2 * j + 1]);
+    lc.out[off] = v[COLS - 1];
+  }
+  b3::hash_felts_c<COLS>([&](int c) { return v[c]; }, d);
+}
+
 template <int MODE>
 __device__ __forceinline__ void merkle_leaf(const MerkleArgs& a, uint64_t i, uint32_t d[8]) {
   if (MODE == 0) {
     uint64_t j = i & ((1ull << a.logB) - 1), t = i >> a.logB;
-    const felt* base = a.src + j * a.n + t;
-    const uint64_t cstride = a.n << a.logB;
-    b3::hash_felts([&](uint32_t c) { return base[c * cstride]; }, a.cols, d);
+    row_digest(a.src + j * a.n + t, a.n << a.logB, a.cols, d);
   } else if (MODE == 1) {
     // natural row i = j + B*t' -> coset j, positions t' + k*R
-    const felt* base = a.src + ((i & ((1ull << a.logB) - 1)) * a.cols) * a.R + (i >> a.logB);
-    b3::hash_felts([&](uint32_t k) { return base[k * a.R]; }, a.cols, d);
+    row_digest(a.src + ((i & ((1ull << a.logB) - 1)) * a.cols) * a.R + (i >> a.logB), a.R, a.cols, d);
   } else if (MODE == 4 || MODE == 5) {  // MODE 0 with lazy GlobalUpdate columns (5: gu_row_shape)
     const uint64_t j = i & ((1ull << a.logB) - 1), t = i >> a.logB;
     const felt* base = a.src + j * a.n + t;
     const felt* prev = a.src + j * a.n + (t == 0 ? a.n - 1 : t - 1);
-    const uint64_t cstride = a.n << a.logB;
-    const felt l = a.gl.l0[j * a.n + t];
-    if constexpr (MODE == 5)
-      gu_row_hash(a.gl, base, prev, cstride, l, d);
-    else
-      b3::hash_felts([&](uint32_t c) { return c < a.gl.wi ? base[c * cstride] : gu_lazy_value(a.gl, base, prev, cstride, l, c); },
-                     a.cols, d);
+    gu_row_digest<MODE>(a.gl, base, prev, a.n << a.logB, a.gl.l0[j * a.n + t], a.cols, d);
   } else if (MODE == 3) {
     // leaf i = j + B*tl sits in chunk k = tl >> logrc, source block j, row tl mod rc
     const uint64_t j = i & ((1ull << a.logB) - 1), tl = i >> a.logB;
@@ -206,14 +186,19 @@ __device__ __forceinline__ void merkle_leaf(const MerkleArgs& a, uint64_t i, uin
   }
 }
 
-template <bool ROLLED = false>
 __device__ __forceinline__ void merge_quad(const uint32_t m[16], uint32_t q, uint32_t& o0, uint32_t& o1) {
   o0 = sel4(q, b3::iv(0), b3::iv(1), b3::iv(2), b3::iv(3));
   o1 = sel4(q, b3::iv(4), b3::iv(5), b3::iv(6), b3::iv(7));
-  if constexpr (ROLLED)
-    compress_quad_r(m, q, b3::CHUNK_START | b3::CHUNK_END | b3::ROOT, o0, o1);
-  else
-    compress_quad(m, q, b3::CHUNK_START | b3::CHUNK_END | b3::ROOT, o0, o1);
+  compress_quad(m, q, b3::CHUNK_START | b3::CHUNK_END | b3::ROOT, o0, o1);
+}
+
+// lane q of a quad holds words q and 4+q of node nd's digest: to the level in sd[] and to the tree (dst)
+__device__ __forceinline__ void quad_store(uint32_t* sd, uint32_t* dst, uint32_t nd, uint32_t q, uint32_t o0,
+                                           uint32_t o1) {
+  sd[nd * 9 + q] = o0;
+  sd[nd * 9 + 4 + q] = o1;
+  dst[q] = o0;
+  dst[4 + q] = o1;
 }
 
 // Quad-cooperative digest of one FRI row of F felts (16 * F bytes: one chunk of
@@ -228,28 +213,61 @@ __device__ __forceinline__ void fri_leaf_quad(const MerkleArgs& a, uint64_t i, u
   o1 = sel4(q, b3::iv(4), b3::iv(5), b3::iv(6), b3::iv(7));
 #pragma unroll
   for (uint32_t blk = 0; blk < NB; blk++) {
-    uint32_t m[16];
+    felt v[4];
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-      felt v = fp::zero();
-      if (k < (int)PER) v = base[(4 * blk + k) * a.R];
-      m[4 * k + 0] = (uint32_t)v.lo;
-      m[4 * k + 1] = (uint32_t)(v.lo >> 32);
-      m[4 * k + 2] = (uint32_t)v.hi;
-      m[4 * k + 3] = (uint32_t)(v.hi >> 32);
-    }
+    for (int k = 0; k < 4; k++) v[k] = k < (int)PER ? base[(4 * blk + k) * a.R] : fp::zero();
+    uint32_t m[16];
+    pack4(v, m);
     const uint32_t fl = (blk == 0 ? b3::CHUNK_START : 0u) | (blk == NB - 1 ? (b3::CHUNK_END | b3::ROOT) : 0u);
     compress_quad(m, q, fl, o0, o1, 16 * PER);
   }
 }
 
-template <bool ROLLED = false>
 __device__ __forceinline__ void merge8(const uint32_t l[8], const uint32_t r[8], uint32_t out[8]) {
   uint32_t m[16];
 #pragma unroll
   for (int i = 0; i < 8; i++) { m[i] = l[i]; m[8 + i] = r[i]; }
   b3::set_iv(out);
-  b3::compress_t<ROLLED>(out, m, 0, 64, b3::CHUNK_START | b3::CHUNK_END | b3::ROOT);
+  b3::compress(out, m, 0, 64, b3::CHUNK_START | b3::CHUNK_END | b3::ROOT);
+}
+
+// The levels s0, s0/2, .. 1 above the 2 * s0 digests a block holds in sd[] (9 words apart),
+// by the whole block: every node goes back to sd[] and to the tree, where the level held in
+// sd[] starts at node `first` and each level above at half the index of the one below. One
+// quad per node from 64 nodes down, one lane per node above. Every thread of the block
+// reaches both barriers of every level: one before the level's reads, one between its reads
+// and its writes.
+__device__ __forceinline__ void lds_levels(uint32_t* sd, uint32_t s0, uint32_t* nodes, uint64_t first) {
+  const uint32_t t = threadIdx.x, nd = t >> 2, q = t & 3;
+  for (uint32_t s = s0; s >= 1; s >>= 1) {
+    first >>= 1;
+    __syncthreads();
+    if (s <= 64) {  // narrow level: one quad per node
+      uint32_t o0 = 0, o1 = 0;
+      if (t < 4 * s) {
+        uint32_t mm[16];
+#pragma unroll
+        for (int i = 0; i < 8; i++) { mm[i] = sd[(2 * nd) * 9 + i]; mm[8 + i] = sd[(2 * nd + 1) * 9 + i]; }
+        merge_quad(mm, q, o0, o1);
+      }
+      __syncthreads();
+      if (t < 4 * s) quad_store(sd, nodes + (first + nd) * 8, nd, q, o0, o1);
+      continue;
+    }
+    uint32_t o[8];
+    if (t < s) {
+      uint32_t l[8], r[8];
+#pragma unroll
+      for (int i = 0; i < 8; i++) { l[i] = sd[(2 * t) * 9 + i]; r[i] = sd[(2 * t + 1) * 9 + i]; }
+      merge8(l, r, o);
+    }
+    __syncthreads();
+    if (t < s) {
+#pragma unroll
+      for (int i = 0; i < 8; i++) sd[t * 9 + i] = o[i];
+      store_digest(nodes + (first + t) * 8, o);
+    }
+  }
 }
 
 __device__ __forceinline__ void merkle_tail_op(const MerkleTail& tl, const uint32_t* root);
@@ -266,21 +284,16 @@ __global__ __launch_bounds__(256) void k_merkle_fused(MerkleArgs a) {
   constexpr uint64_t LB = QUAD ? 64 : 512;        // leaves per block
   const uint64_t cnt = L < LB ? L : LB;           // leaves in this block's subtree
   const uint64_t base = (uint64_t)blockIdx.x * LB;
-  uint64_t lvl, lbase;
-  uint32_t s0;  // nodes of the level above the one held in sd[]
+  uint64_t first;  // node index of the level held in sd[]
+  uint32_t s0;     // nodes of the level above it
   if constexpr (QUAD) {
     const uint32_t nd = t >> 2, q = t & 3;
     if (nd < cnt) {  // the 4 lanes of a quad are active together (DPP)
       uint32_t o0, o1;
       fri_leaf_quad(a, base + nd, q, o0, o1);
-      sd[nd * 9 + q] = o0;
-      sd[nd * 9 + 4 + q] = o1;
-      uint32_t* dst = a.nodes + (L + base + nd) * 8;
-      dst[q] = o0;
-      dst[4 + q] = o1;
+      quad_store(sd, a.nodes + (L + base + nd) * 8, nd, q, o0, o1);
     }
-    lvl = L;
-    lbase = base;
+    first = L + base;
     s0 = (uint32_t)(cnt >> 1);
   } else {
     uint32_t m[8];
@@ -292,54 +305,15 @@ __global__ __launch_bounds__(256) void k_merkle_fused(MerkleArgs a) {
         store_digest(a.nodes + (L + base + 2 * t) * 8, d0);
         store_digest(a.nodes + (L + base + 2 * t + 1) * 8, d1);
       }
-      merge8<false>(d0, d1, m);
+      merge8(d0, d1, m);
       store_digest(a.nodes + ((L >> 1) + (base >> 1) + t) * 8, m);
 #pragma unroll
       for (int i = 0; i < 8; i++) sd[t * 9 + i] = m[i];
     }
-    lvl = L >> 1;
-    lbase = base >> 1;
+    first = (L >> 1) + (base >> 1);
     s0 = (uint32_t)(cnt >> 2);
   }
-  for (uint32_t s = s0; s >= 1; s >>= 1) {
-    __syncthreads();
-    if (s <= 64) {  // narrow level: one quad per node
-      const uint32_t nd = t >> 2, q = t & 3;
-      uint32_t o0 = 0, o1 = 0;
-      if (t < 4 * s) {
-        uint32_t mm[16];
-#pragma unroll
-        for (int i = 0; i < 8; i++) { mm[i] = sd[(2 * nd) * 9 + i]; mm[8 + i] = sd[(2 * nd + 1) * 9 + i]; }
-        merge_quad<false>(mm, q, o0, o1);
-      }
-      lvl >>= 1;
-      lbase >>= 1;
-      __syncthreads();
-      if (t < 4 * s) {
-        sd[nd * 9 + q] = o0;
-        sd[nd * 9 + 4 + q] = o1;
-        uint32_t* dst = a.nodes + (lvl + lbase + nd) * 8;
-        dst[q] = o0;
-        dst[4 + q] = o1;
-      }
-      continue;
-    }
-    uint32_t o[8];
-    if (t < s) {
-      uint32_t l[8], r[8];
-#pragma unroll
-      for (int i = 0; i < 8; i++) { l[i] = sd[(2 * t) * 9 + i]; r[i] = sd[(2 * t + 1) * 9 + i]; }
-      merge8<false>(l, r, o);
-    }
-    lvl >>= 1;
-    lbase >>= 1;
-    __syncthreads();
-    if (t < s) {
-#pragma unroll
-      for (int i = 0; i < 8; i++) sd[t * 9 + i] = o[i];
-      store_digest(a.nodes + (lvl + lbase + t) * 8, o);
-    }
-  }
+  lds_levels(sd, s0, a.nodes, first);
   if (!a.tail.done) return;
   // the last block to finish builds the levels above the G = gridDim.x subtree
   // roots (nodes[G .. 2G), G <= 512) up to nodes[1], then runs the FRI coin step
@@ -360,59 +334,21 @@ __global__ __launch_bounds__(256) void k_merkle_fused(MerkleArgs a) {
         const uint32_t* src = a.nodes + (uint64_t)(G + 2 * nd) * 8;  // the node's two children, adjacent
 #pragma unroll
         for (int k = 0; k < 16; k++) mm[k] = src[k];
-        merge_quad<false>(mm, q, o0, o1);
-        sd[nd * 9 + q] = o0;
-        sd[nd * 9 + 4 + q] = o1;
-        uint32_t* dst = a.nodes + (uint64_t)(G / 2 + nd) * 8;
-        dst[q] = o0;
-        dst[4 + q] = o1;
+        merge_quad(mm, q, o0, o1);
+        quad_store(sd, a.nodes + (uint64_t)(G / 2 + nd) * 8, nd, q, o0, o1);
       }
     } else {
       for (uint32_t i = t; i < G / 2; i += 256) {  // level G/2 from the roots in global memory
         uint32_t l[8], r[8], o[8];
         load_digest(a.nodes + (uint64_t)(G + 2 * i) * 8, l);
         load_digest(a.nodes + (uint64_t)(G + 2 * i + 1) * 8, r);
-        merge8<false>(l, r, o);
+        merge8(l, r, o);
         store_digest(a.nodes + (uint64_t)(G / 2 + i) * 8, o);
 #pragma unroll
         for (int k = 0; k < 8; k++) sd[i * 9 + k] = o[k];
       }
     }
-    for (uint32_t sl = G / 4; sl >= 1; sl >>= 1) {
-      __syncthreads();
-      if (sl <= 64) {  // narrow level: one quad per node
-        const uint32_t nd = t >> 2, q = t & 3;
-        uint32_t o0 = 0, o1 = 0;
-        if (t < 4 * sl) {
-          uint32_t mm[16];
-#pragma unroll
-          for (int k = 0; k < 8; k++) { mm[k] = sd[(2 * nd) * 9 + k]; mm[8 + k] = sd[(2 * nd + 1) * 9 + k]; }
-          merge_quad<false>(mm, q, o0, o1);
-        }
-        __syncthreads();
-        if (t < 4 * sl) {
-          sd[nd * 9 + q] = o0;
-          sd[nd * 9 + 4 + q] = o1;
-          uint32_t* dst = a.nodes + (uint64_t)(sl + nd) * 8;
-          dst[q] = o0;
-          dst[4 + q] = o1;
-        }
-        continue;
-      }
-      uint32_t o[8];
-      if (t < sl) {
-        uint32_t l[8], r[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) { l[k] = sd[(2 * t) * 9 + k]; r[k] = sd[(2 * t + 1) * 9 + k]; }
-        merge8<false>(l, r, o);
-      }
-      __syncthreads();
-      if (t < sl) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) sd[t * 9 + k] = o[k];
-        store_digest(a.nodes + (uint64_t)(sl + t) * 8, o);
-      }
-    }
+    lds_levels(sd, G / 4, a.nodes, G / 2);
   }
   __syncthreads();
   if (t == 0) *a.tail.done = 0;  // ready for the next launch on this stream
@@ -450,31 +386,20 @@ __global__ __launch_bounds__(256) void k_merkle_leaf2(MerkleArgs a) {
   const uint64_t lane = blockIdx.x * (uint64_t)256 + threadIdx.x;
   if (lane >= (a.L >> 1)) return;
   const uint64_t cstride = a.n << a.logB, bmask = (1ull << a.logB) - 1;
-  constexpr int RD = DERIVE ? COLS - 1 : COLS;  // columns read from the source
   felt v[2][COLS], h[2];
+  uint64_t off[2];
 #pragma unroll
   for (int r = 0; r < 2; r++) {
     const uint64_t i = 2 * lane + r;
-    const uint64_t off = (i & bmask) * a.n + (i >> a.logB);
-    const felt* base = a.src + off;
-#pragma unroll
-    for (int c = 0; c < RD; c++) v[r][c] = base[c * cstride];
-    if constexpr (DERIVE) h[r] = a.lc.H[off];
+    off[r] = (i & bmask) * a.n + (i >> a.logB);
+    narrow_row_load<COLS, DERIVE>(a.src + off[r], cstride, a.lc, off[r], v[r], h[r]);
   }
-  if constexpr (DERIVE) {
+  uint32_t d[2][8], m[8];
 #pragma unroll
-    for (int r = 0; r < 2; r++) {
-      const uint64_t i = 2 * lane + r, j = i & bmask;
-      v[r][COLS - 1] = derive_last<COLS>(v[r], h[r], a.lc.kap[2 * j], a.lc.kap[2 * j + 1]);
-      a.lc.out[j * a.n + (i >> a.logB)] = v[r][COLS - 1];
-    }
-  }
-  uint32_t d0[8], d1[8], m[8];
-  b3::hash_felts_c<COLS>([&](int c) { return v[0][c]; }, d0);
-  b3::hash_felts_c<COLS>([&](int c) { return v[1][c]; }, d1);
-  store_digest(a.nodes + (a.L + 2 * lane) * 8, d0);
-  store_digest(a.nodes + (a.L + 2 * lane + 1) * 8, d1);
-  merge8(d0, d1, m);
+  for (int r = 0; r < 2; r++) narrow_row_digest<COLS, DERIVE>(v[r], h[r], a.lc, (2 * lane + r) & bmask, off[r], d[r]);
+  store_digest(a.nodes + (a.L + 2 * lane) * 8, d[0]);
+  store_digest(a.nodes + (a.L + 2 * lane + 1) * 8, d[1]);
+  merge8(d[0], d[1], m);
   store_digest(a.nodes + ((a.L >> 1) + lane) * 8, m);
 }
 
@@ -566,35 +491,18 @@ __global__ __launch_bounds__(TPB, MODE == 4 || MODE == 5 ? 4 : 1) void k_leaf_ha
   const uint64_t t = (sd << logrr) + ((uint64_t)k << logrc) + tc;
   const uint64_t rows = 1ull << logrows;
   uint32_t d[8];
-  if constexpr (MODE == 0 && COLS > 0) {
-    const felt* base = src + jl * n + t;
-    const uint64_t cstride = n << logBl;
-    felt v[COLS];
-    constexpr int RD = DERIVE ? COLS - 1 : COLS;
-#pragma unroll
-    for (int c = 0; c < RD; c++) v[c] = base[c * cstride];
-    if constexpr (DERIVE) {  // LastCol over the rank's cosets (lc.kap offset to coset j0)
-      v[COLS - 1] = derive_last<COLS>(v, lc.H[jl * n + t], lc.kap[2 * jl], lc.kap[2 * jl + 1]);
-      lc.out[jl * n + t] = v[COLS - 1];
-    }
-    b3::hash_felts_c<COLS>([&](int c) { return v[c]; }, d);
+  if constexpr (MODE == 0 && COLS > 0) {  // (DERIVE: LastCol over the rank's cosets, lc.kap offset to coset j0)
+    felt v[COLS], h;
+    narrow_row_load<COLS, DERIVE>(src + jl * n + t, n << logBl, lc, jl * n + t, v, h);
+    narrow_row_digest<COLS, DERIVE>(v, h, lc, jl, jl * n + t, d);
   } else if (MODE == 0) {  // LDE row t of coset jl: (c*Bl + jl)*n + t
-    const felt* base = src + jl * n + t;
-    const uint64_t cstride = n << logBl;
-    b3::hash_felts([&](uint32_t c) { return base[c * cstride]; }, cols, d);
+    row_digest(src + jl * n + t, n << logBl, cols, d);
   } else if (MODE == 4 || MODE == 5) {  // MODE 0 with lazy GlobalUpdate columns (5: gu_row_shape)
     const felt* base = src + jl * n + t;
     const felt* prev = src + jl * n + (t == 0 ? n - 1 : t - 1);
-    const uint64_t cstride = n << logBl;
-    const felt l = gl.l0[jl * n + t];
-    if constexpr (MODE == 5)
-      gu_row_hash(gl, base, prev, cstride, l, d);
-    else
-      b3::hash_felts([&](uint32_t c) { return c < gl.wi ? base[c * cstride] : gu_lazy_value(gl, base, prev, cstride, l, c); },
-                     cols, d);
+    gu_row_digest<MODE>(gl, base, prev, n << logBl, gl.l0[jl * n + t], cols, d);
   } else {  // FRI row: positions t + k*rows of coset jl (16*rows per coset)
-    const felt* base = src + (jl << (logrows + 4)) + t;
-    b3::hash_felts([&](uint32_t kk) { return base[kk * rows]; }, cols, d);
+    row_digest(src + (jl << (logrows + 4)) + t, rows, cols, d);
   }
   store_digest(send + ((((sd << logBl) + jl) << logrc) + tc) * 8, d);
 }
@@ -614,21 +522,10 @@ __global__ __launch_bounds__(TPB) void k_leaf_unpack(const uint32_t* __restrict_
   store_digest(nodes + (L + j + (tl << logB)) * 8, d);
 }
 
-// Fiat-Shamir step of the FRI commit loop on the device (winter-crypto
-// DefaultRandomCoin<Blake3_256>: reseed = merge(seed, root), counter = 0; draw
-// = first merge_with_int(seed, ++counter) whose low 16 bytes are < p). `root`
-// is the layer's Merkle root; the host replays the same steps afterwards and
-// checks every alpha. coin = [seed words 0..8), alphas[l], roots[l] (8 words).
 // ---------------------------------------------------------- device transcript
 // winter-crypto DefaultRandomCoin<Blake3_256> on the device: seed = 8 LE words;
 // reseed(d) = BLAKE3(seed || d); draw = first 16 B of BLAKE3(seed || ctr_le64),
 // ctr = 1, 2, ... since the last reseed, rejected while >= p.
-__device__ __forceinline__ void dcoin_reseed(uint32_t s[8], const uint32_t d[8]) {
-  uint32_t m[16];
-  for (int i = 0; i < 8; i++) { m[i] = s[i]; m[8 + i] = d[i]; }
-  b3::set_iv(s);
-  b3::compress_r(s, m, 0, 64, b3::CHUNK_START | b3::CHUNK_END | b3::ROOT);
-}
 __device__ __forceinline__ felt dcoin_candidate(const uint32_t s[8], uint64_t ctr) {
   uint32_t m[16], o[8];
   for (int i = 0; i < 8; i++) m[i] = s[i];
@@ -1147,85 +1044,19 @@ __global__ __launch_bounds__(128) void k_gather_full(FullGatherArgs a, const uin
   }
 }
 
-// fold-by-16: u = iDFT16(row) (unscaled), result = (1/16) sum_k u_k beta^k,
-// beta = alpha / x_r; eps_inv[m] = w_16^-m for m < 8, eps_inv[8] = 1/16.
-// Layer evaluations are coset-major (coset jl of Bl, m = 16*m16 positions):
-// local row q = jl*m16 + t' is the natural row r = (j0 + jl) + B*t' whose 16
-// values sit at positions t' + k*m16 of the same coset; out is coset-major.
-__device__ __forceinline__ felt fri_fold_row(const felt* __restrict__ E, uint64_t q, uint32_t logm16, uint32_t j0,
-                                             uint32_t logB, const felt* alpha_p, felt off_inv,
-                                             const felt* __restrict__ itw_lev, const felt* __restrict__ eps_inv) {
-  const uint64_t m16 = 1ull << logm16;
-  const uint64_t jl = q >> logm16, tp = q & (m16 - 1);
-  const uint64_t r = (j0 + jl) + (tp << logB);
-  const felt* src = E + (jl << (logm16 + 4)) + tp;
-  felt v[16];
-#pragma unroll
-  for (int k = 0; k < 16; k++) v[k] = src[k * m16];
-  // Gentleman-Sande, natural in -> bit-reversed out (fully unrolled, constant indices)
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    felt x = v[i], y = v[i + 8];
-    v[i] = add(x, y);
-    v[i + 8] = i == 0 ? sub(x, y) : mul(sub(x, y), eps_inv[i]);
-  }
-#pragma unroll
-  for (int blk = 0; blk < 16; blk += 8) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      felt x = v[blk + i], y = v[blk + i + 4];
-      v[blk + i] = add(x, y);
-      v[blk + i + 4] = i == 0 ? sub(x, y) : mul(sub(x, y), eps_inv[2 * i]);
-    }
-  }
-#pragma unroll
-  for (int blk = 0; blk < 16; blk += 4) {
-    felt x0 = v[blk], y0 = v[blk + 2], x1 = v[blk + 1], y1 = v[blk + 3];
-    v[blk] = add(x0, y0);
-    v[blk + 2] = sub(x0, y0);
-    v[blk + 1] = add(x1, y1);
-    v[blk + 3] = mul(sub(x1, y1), eps_inv[4]);
-  }
-#pragma unroll
-  for (int blk = 0; blk < 16; blk += 2) {
-    felt x = v[blk], y = v[blk + 1];
-    v[blk] = add(x, y);
-    v[blk + 1] = sub(x, y);
-  }
-  felt beta = mul(*alpha_p, mul(off_inv, itw_lev[r]));
-  // Horner over k = 15..0 with u_k = v[rev4(k)], rev4 = {0,8,4,12,2,10,6,14,1,9,5,13,3,11,7,15}
-  // (Estrin's scheme measured slower: 18 products instead of 15, and one wave
-  // per SIMD issues in order, so the shorter chain buys nothing)
-  felt acc = v[15];
-  acc = add(mul(acc, beta), v[7]);
-  acc = add(mul(acc, beta), v[11]);
-  acc = add(mul(acc, beta), v[3]);
-  acc = add(mul(acc, beta), v[13]);
-  acc = add(mul(acc, beta), v[5]);
-  acc = add(mul(acc, beta), v[9]);
-  acc = add(mul(acc, beta), v[1]);
-  acc = add(mul(acc, beta), v[14]);
-  acc = add(mul(acc, beta), v[6]);
-  acc = add(mul(acc, beta), v[10]);
-  acc = add(mul(acc, beta), v[2]);
-  acc = add(mul(acc, beta), v[12]);
-  acc = add(mul(acc, beta), v[4]);
-  acc = add(mul(acc, beta), v[8]);
-  acc = add(mul(acc, beta), v[0]);
-  return mul(acc, eps_inv[8]);
-}
-
-// fold-by-F for F = 2, 4, 8 (same layout, F values per row at positions t' + k*mF
-// of coset jl, mF = m / F): the row's degree-< F polynomial through (x_r w_F^k, v_k)
-// at alpha, as u = iDFT_F(row) (unscaled) and (1/F) sum_k u_k beta^k. w_F^-i is
-// eps_inv[i * 16 / F]; 1/8, 1/4, 1/2 follow 1/16 at eps_inv[9..12). F = 2 has no
-// twiddle: (v0 + v1)/2 + beta (v0 - v1)/2.
+// fold-by-F for F = 2, 4, 8, 16 by one lane: the row's degree-< F polynomial through
+// (x_r w_F^k, v_k) at alpha, as u = iDFT_F(row) (unscaled) and (1/F) sum_k u_k beta^k,
+// beta = alpha / x_r. Layer evaluations are coset-major (coset jl of Bl, m = F*mF
+// positions): local row q = jl*mF + t' is the natural row r = (j0 + jl) + B*t' whose F
+// values sit at positions t' + k*mF of the same coset; out is coset-major.
+// eps_inv[m] = w_16^-m for m < 8, so w_F^-i is eps_inv[i * 16 / F]; 1/16, 1/8, 1/4, 1/2
+// are eps_inv[8..12). F = 2 has no twiddle: (v0 + v1)/2 + beta (v0 - v1)/2.
 template <int F>
 __device__ __forceinline__ felt fri_fold_row_f(const felt* __restrict__ E, uint64_t q, uint32_t logmF, uint32_t j0,
                                                uint32_t logB, const felt* alpha_p, felt off_inv,
                                                const felt* __restrict__ itw_lev, const felt* __restrict__ eps_inv) {
-  static_assert(F == 2 || F == 4 || F == 8, "fold-16 has its own functions");
-  constexpr int LOGF = F == 2 ? 1 : (F == 4 ? 2 : 3);
+  static_assert(F == 2 || F == 4 || F == 8 || F == 16, "folding factor");
+  constexpr int LOGF = F == 2 ? 1 : (F == 4 ? 2 : (F == 8 ? 3 : 4));
   const uint64_t mF = 1ull << logmF;
   const uint64_t jl = q >> logmF, tp = q & (mF - 1);
   const uint64_t r = (j0 + jl) + (tp << logB);
@@ -1245,7 +1076,9 @@ __device__ __forceinline__ felt fri_fold_row_f(const felt* __restrict__ E, uint6
       else v[lo + span] = mul(sub(x, y), eps_inv[i * (8 / span)]);
     });
   });
-  // Horner over k = F-1..0 with u_k = v[rev(k)]
+  // Horner over k = F-1..0 with u_k = v[rev(k)] (for F = 16 Estrin's scheme measured
+  // slower: 18 products instead of 15, and one wave per SIMD issues in order, so the
+  // shorter chain buys nothing)
   felt acc = v[kc::rev_const(F - 1, LOGF)];
   static_for<1, F>([&](auto kk) { acc = add(mul(acc, beta), v[kc::rev_const(F - 1 - decltype(kk)::value, LOGF)]); });
   return mul(acc, eps_inv[12 - LOGF]);
@@ -1341,16 +1174,6 @@ __global__ __launch_bounds__(TPB) void k_fri_fold16_quad(const felt* __restrict_
   if (q < rows && qd == 0) out[q] = v;
 }
 
-__global__ __launch_bounds__(TPB) void k_fri_fold16(const felt* __restrict__ E, uint64_t rows, uint32_t logm16,
-                                                    uint32_t j0, uint32_t logB, const felt* __restrict__ alpha_p,
-                                                    felt off_inv,
-                                                    const felt* __restrict__ itw_lev,
-                                                    const felt* __restrict__ eps_inv, felt* __restrict__ out) {
-  const uint64_t q = blockIdx.x * (uint64_t)TPB + threadIdx.x;
-  if (q >= rows) return;
-  out[q] = fri_fold_row(E, q, logm16, j0, logB, alpha_p, off_inv, itw_lev, eps_inv);
-}
-
 template <int F>
 __global__ __launch_bounds__(TPB) void k_fri_fold(const felt* __restrict__ E, uint64_t rows, uint32_t logmF,
                                                   uint32_t j0, uint32_t logB, const felt* __restrict__ alpha_p,
@@ -1385,30 +1208,9 @@ __global__ __launch_bounds__(512) void k_fri_tail(FriTailArgs a) {
     if (nd < R) {  // whole quads
       uint32_t o0, o1;
       fri_leaf_quad<F>(ma, nd, q, o0, o1);
-      sd[nd * 9 + q] = o0;
-      sd[nd * 9 + 4 + q] = o1;
-      uint32_t* dst = y.nodes + (uint64_t)(R + nd) * 8;
-      dst[q] = o0;
-      dst[4 + q] = o1;
+      quad_store(sd, y.nodes + (uint64_t)(R + nd) * 8, nd, q, o0, o1);
     }
-    for (uint32_t s = R >> 1; s >= 1; s >>= 1) {
-      __syncthreads();
-      uint32_t o0 = 0, o1 = 0;
-      if (nd < s) {
-        uint32_t mm[16];
-#pragma unroll
-        for (int i = 0; i < 8; i++) { mm[i] = sd[(2 * nd) * 9 + i]; mm[8 + i] = sd[(2 * nd + 1) * 9 + i]; }
-        merge_quad<false>(mm, q, o0, o1);
-      }
-      __syncthreads();
-      if (nd < s) {
-        sd[nd * 9 + q] = o0;
-        sd[nd * 9 + 4 + q] = o1;
-        uint32_t* dst = y.nodes + (uint64_t)(s + nd) * 8;
-        dst[q] = o0;
-        dst[4 + q] = o1;
-      }
-    }
+    lds_levels(sd, R >> 1, y.nodes, R);  // at most 64 nodes per level: quad merges only
     __syncthreads();
     if (t < 4) {
       uint32_t r[8];
@@ -1451,6 +1253,20 @@ static void merkle_pass(Prof& prof, hipStream_t s, const MerkleArgs& a, const ch
   LAUNCH(prof, name, s, bytes, hipLaunchKernelGGL((k_merkle_lane<MODE, H>), g, dim3(256), 0, s, a));
 }
 
+// one k_merkle_fused<MODE, QUAD> launch over the a.L leaves (MODE 2: nodes) of a. With a tail
+// counter and at most 512 blocks, the last block finishes the tree and runs the tail's op:
+// returns 0 then, otherwise the number of subtree roots the launch leaves (one per block)
+template <int MODE, bool QUAD = false>
+static uint64_t merkle_fused_pass(Prof& prof, hipStream_t s, MerkleArgs a, const MerkleTail* tail, const char* name,
+                                  double bytes) {
+  const uint64_t per = QUAD ? 64 : 512, blocks = (a.L + per - 1) / per;
+  const bool finish = tail && tail->done && blocks <= 512;
+  if (finish) a.tail = *tail;
+  LAUNCH(prof, name, s, bytes,
+         hipLaunchKernelGGL((k_merkle_fused<MODE, QUAD>), dim3((uint32_t)blocks), dim3(256), 0, s, a));
+  return finish ? 0 : blocks;
+}
+
 // upper levels: wide levels by lane passes (4 levels each), the narrow top by
 // the LDS-fused kernel (9 levels per launch, parallel tail)
 bool merkle_upper(Prof& prof, hipStream_t s, uint32_t* nodes, uint64_t L, const MerkleTail* tail) {
@@ -1470,13 +1286,8 @@ bool merkle_upper(Prof& prof, hipStream_t s, uint32_t* nodes, uint64_t L, const 
       merkle_pass<2, 2>(prof, s, a, "merkle_upper", (double)L * 32.0 * 1.5);
       L >>= 2;
     } else {
-      uint64_t blocks = (L + 511) / 512;
-      const bool finish = tail && tail->done && blocks <= 512;  // this launch completes the tree
-      if (finish) a.tail = *tail;
-      LAUNCH(prof, "merkle_top9", s, (double)L * 64.0,
-             hipLaunchKernelGGL(k_merkle_fused<2>, dim3((uint32_t)blocks), dim3(256), 0, s, a));
-      if (finish) return true;
-      L = L >= 512 ? L / 512 : 1;
+      L = merkle_fused_pass<2>(prof, s, a, tail, "merkle_top9", (double)L * 64.0);
+      if (L == 0) return true;  // that launch completed the tree
     }
   }
   return false;
@@ -1529,13 +1340,8 @@ bool launch_merkle_lde(Prof& prof, hipStream_t s, const felt* lde, uint32_t cols
   return merkle_upper(prof, s, nodes, L >> H, tail);
 }
 
-// largest FRI layer (log2 rows) whose leaves are hashed by quads (tuned with
-// tests/native/kbench_top.cpp, which builds this file with -DZKP_FRI_QUAD_TUNING)
-#ifdef ZKP_FRI_QUAD_TUNING
-uint32_t fri_quad_max_log = 13;
-#else
+// largest FRI layer (log2 rows) whose leaves are hashed by quads
 static constexpr uint32_t fri_quad_max_log = 13;
-#endif
 
 bool launch_merkle_fri(Prof& prof, hipStream_t s, const felt* E, uint64_t m16, uint32_t logB, uint32_t F,
                        uint32_t* nodes, const MerkleTail* tail) {
@@ -1547,56 +1353,25 @@ bool launch_merkle_fri(Prof& prof, hipStream_t s, const felt* E, uint64_t m16, u
   a.cols = F;
   a.nodes = nodes;
   a.L = R;
-  if (F == 16 && R <= (1ull << fri_quad_max_log)) {  // profiles/r02_ab_quad_leaves.txt
-    // small layers (<= 2^13 rows): one quad of lanes per row, 64 rows and 6 levels
-    // per block. At 2^15 rows the quads' extra instructions made it slower
-    // (72 vs 53 us); at 2^11 / 2^7 / 2^3 rows it is faster (30/22/21 vs 40/34/29 us)
-    uint64_t blocks = (R + 63) / 64;
-    const bool finish = tail && tail->done && blocks <= 512;
-    if (finish) a.tail = *tail;
-    LAUNCH(prof, "merkle_fri", s, (double)R * (F * 16.0 + 64.0),
-           hipLaunchKernelGGL((k_merkle_fused<1, true>), dim3((uint32_t)blocks), dim3(256), 0, s, a));
-    if (finish) return true;
-    return merkle_upper(prof, s, nodes, blocks, tail);
+  const double bytes = (double)R * (F * 16.0 + 64.0);
+  if (R > (1ull << 16)) {
+    merkle_pass<1, 2>(prof, s, a, "merkle_fri", bytes);
+    return merkle_upper(prof, s, nodes, R >> 2, tail);
   }
-  if (R <= (1ull << 16)) {
-    // small layers: a lane subtree would serialise 19 compressions per lane on a
-    // few waves; hash 2 rows per thread and build 9 levels per block instead
-    uint64_t blocks = (R + 511) / 512;
-    const bool finish = tail && tail->done && blocks <= 512;
-    if (finish) a.tail = *tail;
-    LAUNCH(prof, "merkle_fri", s, (double)R * (F * 16.0 + 64.0),
-           hipLaunchKernelGGL(k_merkle_fused<1>, dim3((uint32_t)blocks), dim3(256), 0, s, a));
-    if (finish) return true;
-    return merkle_upper(prof, s, nodes, R >= 512 ? R / 512 : 1, tail);
-  }
-  merkle_pass<1, 2>(prof, s, a, "merkle_fri", (double)R * (F * 16.0 + 64.0));  // R > 2^16
-  return merkle_upper(prof, s, nodes, R >> 2, tail);
+  // small layers: a lane subtree would serialise 19 compressions per lane on a few waves;
+  // hash 2 rows per thread and build 9 levels per block instead. Up to 2^13 rows of 16:
+  // one quad of lanes per row, 64 rows and 6 levels per block (profiles/r02_ab_quad_leaves.txt).
+  // At 2^15 rows the quads' extra instructions made it slower (72 vs 53 us); at
+  // 2^11 / 2^7 / 2^3 rows it is faster (30/22/21 vs 40/34/29 us)
+  const uint64_t roots = F == 16 && R <= (1ull << fri_quad_max_log)
+                             ? merkle_fused_pass<1, true>(prof, s, a, tail, "merkle_fri", bytes)
+                             : merkle_fused_pass<1>(prof, s, a, tail, "merkle_fri", bytes);
+  return roots == 0 || merkle_upper(prof, s, nodes, roots, tail);
 }
 
 void preload_merkle_module() {
   hipFuncAttributes fa;
-  (void)hipFuncGetAttributes(&fa, (const void*)k_merkle_level);
-}
-
-void launch_leaf_hash_lde(Prof& prof, hipStream_t s, const felt* lde, uint32_t cols, uint32_t logB, uint64_t n,
-                          uint32_t* nodes, uint64_t L) {
-  LAUNCH(prof, "leaf_hash_lde", s, (double)L * (cols * 16.0 + 32.0),
-         hipLaunchKernelGGL(k_leaf_hash_lde, dim3(blocks_for(L)), dim3(TPB), 0, s, lde, cols, logB, n, nodes, L));
-}
-
-void launch_leaf_hash_fri(Prof& prof, hipStream_t s, const felt* E, uint64_t R, uint32_t F, uint32_t* nodes) {
-  LAUNCH(prof, "leaf_hash_fri", s, (double)R * (F * 16.0 + 32.0),
-         hipLaunchKernelGGL(k_leaf_hash_fri, dim3(blocks_for(R)), dim3(TPB), 0, s, E, R, F, nodes));
-}
-
-void launch_merkle_tree(Prof& prof, hipStream_t s, uint32_t* nodes, uint64_t L) {
-  uint64_t lvl = L / 2;
-  for (; lvl >= 2048; lvl >>= 1)
-    LAUNCH(prof, "merkle_level", s, (double)lvl * 96.0,
-           hipLaunchKernelGGL(k_merkle_level, dim3(blocks_for(lvl)), dim3(TPB), 0, s, nodes, lvl));
-  if (lvl >= 1)
-    LAUNCH(prof, "merkle_top", s, (double)lvl * 2.0 * 96.0, hipLaunchKernelGGL(k_merkle_top, dim3(1), dim3(1024), 0, s, nodes, lvl));
+  (void)hipFuncGetAttributes(&fa, (const void*)k_coin_fri_layer);
 }
 
 void launch_grind(Prof& prof, hipStream_t s, const uint32_t* seed_words, const uint32_t* seed_dev, uint64_t base,
@@ -1658,28 +1433,24 @@ void launch_fri_fold(Prof& prof, hipStream_t s, const felt* E, uint64_t m16, uin
   uint32_t logm16 = 0;
   while ((1ull << logm16) < m16) logm16++;
   const uint64_t rows = m16 * Bl;
-  if (F != 16) {  // m16 = m / F here: one lane per row at every size (rows of 2, 4, 8 are too short to share)
+  // F = 16 up to 2^15 rows: the layer is latency-bound (under one wave per SIMD), and a quad
+  // per row shortens the chain; above that the one-lane form issues fewer products
+  if (F == 16 && rows <= (1ull << 15)) {
+    LAUNCH(prof, "fri_fold16", s, (double)rows * (16 * 16.0 + 16.0),
+           hipLaunchKernelGGL(k_fri_fold16_quad, dim3(blocks_for(rows * 4)), dim3(TPB), 0, s, E, rows, logm16, j0,
+                              logB, alpha, off_inv, lev, eps_inv, out));
+    return;
+  }
+  // m16 = m / F here: one lane per row (rows of 2, 4, 8 are too short to share, at every size)
 #define ZKP_FOLD(FF)                                                                                             \
   case FF:                                                                                                       \
     LAUNCH(prof, "fri_fold" #FF, s, (double)rows * (FF * 16.0 + 16.0),                                           \
            hipLaunchKernelGGL(k_fri_fold<FF>, dim3(blocks_for(rows)), dim3(TPB), 0, s, E, rows, logm16, j0, logB, \
                               alpha, off_inv, lev, eps_inv, out));                                               \
     return;
-    switch (F) { ZKP_FOLD(2) ZKP_FOLD(4) ZKP_FOLD(8) }
+  switch (F) { ZKP_FOLD(2) ZKP_FOLD(4) ZKP_FOLD(8) ZKP_FOLD(16) }
 #undef ZKP_FOLD
-    launch_fail(ZKP_ERR_DEVICE, "internal: FRI folding factor");
-  }
-  // up to 2^15 rows the layer is latency-bound (under one wave per SIMD): a quad
-  // per row shortens the chain; above that the one-lane form issues fewer products
-  if (rows <= (1ull << 15)) {
-    LAUNCH(prof, "fri_fold16", s, (double)rows * (16 * 16.0 + 16.0),
-           hipLaunchKernelGGL(k_fri_fold16_quad, dim3(blocks_for(rows * 4)), dim3(TPB), 0, s, E, rows, logm16, j0,
-                              logB, alpha, off_inv, lev, eps_inv, out));
-    return;
-  }
-  LAUNCH(prof, "fri_fold16", s, (double)rows * (16 * 16.0 + 16.0),
-         hipLaunchKernelGGL(k_fri_fold16, dim3(blocks_for(rows)), dim3(TPB), 0, s, E, rows, logm16, j0, logB, alpha,
-                            off_inv, lev, eps_inv, out));
+  launch_fail(ZKP_ERR_DEVICE, "internal: FRI folding factor");
 }
 
 void launch_fri_tail(Prof& prof, hipStream_t s, const FriTailArgs& a) {
@@ -1690,13 +1461,11 @@ void launch_fri_tail(Prof& prof, hipStream_t s, const FriTailArgs& a) {
       launch_fail(ZKP_ERR_DEVICE, "internal: FRI tail layer over 128 rows");
     if (logrows < 1) launch_fail(ZKP_ERR_DEVICE, "internal: FRI tail layer of one row");
   }
-  switch (a.F) {
-    case 2: LAUNCH(prof, "fri_tail", s, 0.0, hipLaunchKernelGGL(k_fri_tail<2>, dim3(1), dim3(512), 0, s, a)); break;
-    case 4: LAUNCH(prof, "fri_tail", s, 0.0, hipLaunchKernelGGL(k_fri_tail<4>, dim3(1), dim3(512), 0, s, a)); break;
-    case 8: LAUNCH(prof, "fri_tail", s, 0.0, hipLaunchKernelGGL(k_fri_tail<8>, dim3(1), dim3(512), 0, s, a)); break;
-    case 16: LAUNCH(prof, "fri_tail", s, 0.0, hipLaunchKernelGGL(k_fri_tail<16>, dim3(1), dim3(512), 0, s, a)); break;
-    default: launch_fail(ZKP_ERR_DEVICE, "internal: FRI folding factor");
-  }
+#define ZKP_TAIL(FF) \
+  case FF: LAUNCH(prof, "fri_tail", s, 0.0, hipLaunchKernelGGL(k_fri_tail<FF>, dim3(1), dim3(512), 0, s, a)); return;
+  switch (a.F) { ZKP_TAIL(2) ZKP_TAIL(4) ZKP_TAIL(8) ZKP_TAIL(16) }
+#undef ZKP_TAIL
+  launch_fail(ZKP_ERR_DEVICE, "internal: FRI folding factor");
 }
 
 void launch_leaf_hash_shard(Prof& prof, hipStream_t s, int mode, const felt* src, uint64_t n, uint32_t cols,
@@ -1707,28 +1476,20 @@ void launch_leaf_hash_shard(Prof& prof, hipStream_t s, int mode, const felt* src
   const dim3 g(blocks_for(cnt));
   const LastCol lcv = lc ? *lc : LastCol{};
   const GuLazy glv = gl ? *gl : GuLazy{};
-#define ZKP_SHARD_LEAF(CC)                                                                                   \
-  case CC:                                                                                                   \
-    LAUNCH(prof, "leaf_hash_shard", s, bytes,                                                                \
-           hipLaunchKernelGGL((k_leaf_hash_shard<0, CC>), g, dim3(TPB), 0, s, src, n, cols, logBl, logrows, \
-                              logrr, logK, k, send, lcv, glv));                                                   \
-    break;
-#define ZKP_SHARD_LEAFD(CC)                                                                                  \
-  case CC:                                                                                                   \
-    LAUNCH(prof, "leaf_hash_shard", s, bytes,                                                                \
-           hipLaunchKernelGGL((k_leaf_hash_shard<0, CC, true>), g, dim3(TPB), 0, s, src, n, cols, logBl,    \
-                              logrows, logrr, logK, k, send, lcv, glv));                                          \
-    break;
+  // k_leaf_hash_shard<MODE[, COLS[, DERIVE]]> over the chunk's rows
+#define ZKP_SHARD(BYTES, ...)                                                                                    \
+  LAUNCH(prof, "leaf_hash_shard", s, BYTES,                                                                      \
+         hipLaunchKernelGGL((k_leaf_hash_shard<__VA_ARGS__>), g, dim3(TPB), 0, s, src, n, cols, logBl, logrows, \
+                            logrr, logK, k, send, lcv, glv))
+#define ZKP_SHARD_LEAF(CC) case CC: ZKP_SHARD(bytes, 0, CC); break;
+#define ZKP_SHARD_LEAFD(CC) case CC: ZKP_SHARD(bytes, 0, CC, true); break;
   if (gl) {  // lazy GlobalUpdate columns
     if (mode != 0) launch_fail(ZKP_ERR_DEVICE, "internal: lazy columns in a FRI leaf pass");
+    const double stored = (double)cnt * (gl->wi * 16.0 + 32.0);
     if (gu_row_shape(cols, *gl))
-      LAUNCH(prof, "leaf_hash_shard", s, (double)cnt * (gl->wi * 16.0 + 32.0),
-             hipLaunchKernelGGL(k_leaf_hash_shard<5>, g, dim3(TPB), 0, s, src, n, cols, logBl, logrows, logrr, logK,
-                                k, send, lcv, glv));
+      ZKP_SHARD(stored, 5);
     else
-      LAUNCH(prof, "leaf_hash_shard", s, (double)cnt * (gl->wi * 16.0 + 32.0),
-             hipLaunchKernelGGL(k_leaf_hash_shard<4>, g, dim3(TPB), 0, s, src, n, cols, logBl, logrows, logrr, logK,
-                                k, send, lcv, glv));
+      ZKP_SHARD(stored, 4);
   } else if (lc) {  // the caller checked merkle_can_derive
     if (mode != 0 || cols < 2 || cols > 8) launch_fail(ZKP_ERR_DEVICE, "internal: derived-column shard leaf shape");
     switch (cols) { ZKP_SHARD_LEAFD(2) ZKP_SHARD_LEAFD(3) ZKP_SHARD_LEAFD(4) ZKP_SHARD_LEAFD(5)
@@ -1736,17 +1497,15 @@ void launch_leaf_hash_shard(Prof& prof, hipStream_t s, int mode, const felt* src
   } else if (mode == 0 && cols <= 8) {
     switch (cols) { ZKP_SHARD_LEAF(1) ZKP_SHARD_LEAF(2) ZKP_SHARD_LEAF(3) ZKP_SHARD_LEAF(4) ZKP_SHARD_LEAF(5)
                     ZKP_SHARD_LEAF(6) ZKP_SHARD_LEAF(7) ZKP_SHARD_LEAF(8) }
-  } else if (mode == 0)
-    LAUNCH(prof, "leaf_hash_shard", s, bytes,
-           hipLaunchKernelGGL(k_leaf_hash_shard<0>, g, dim3(TPB), 0, s, src, n, cols, logBl,
-                              logrows, logrr, logK, k, send, lcv, glv));
-  else
-    LAUNCH(prof, "leaf_hash_shard", s, (double)cnt * (cols * 16.0 + 32.0),
-           hipLaunchKernelGGL(k_leaf_hash_shard<1>, dim3(blocks_for(cnt)), dim3(TPB), 0, s, src, n, cols, logBl,
-                              logrows, logrr, logK, k, send, lcv, glv));
-}
+  } else if (mode == 0) {
+    ZKP_SHARD(bytes, 0);
+  } else {
+    ZKP_SHARD(bytes, 1);
+  }
 #undef ZKP_SHARD_LEAFD
 #undef ZKP_SHARD_LEAF
+#undef ZKP_SHARD
+}
 
 void launch_merkle_from_shards(Prof& prof, hipStream_t s, const uint32_t* recv, uint32_t logB, uint32_t logrr,
                                uint32_t logK, uint32_t* nodes, uint32_t* done) {
@@ -1790,7 +1549,7 @@ __global__ __launch_bounds__(256) void k_shard_top(const uint32_t* __restrict__ 
       uint32_t l[8], r[8], o[8];
       load_digest(top + (2 * (h + t)) * 8, l);
       load_digest(top + (2 * (h + t) + 1) * 8, r);
-      merge8<false>(l, r, o);
+      merge8(l, r, o);
       store_digest(top + (h + t) * 8, o);
     }
   }

@@ -75,12 +75,9 @@ void launch_build_coset_scale(Prof& prof, hipStream_t s, felt* S, uint32_t logn,
                               const felt* tw, uint32_t logN, const felt* glo, const felt* ghi, felt ninv);
 
 // ---------------------------------------------------------------- hashing
-// leaves L (= n*B) of a coset-major LDE matrix (cols x B x n) -> nodes[L + i] (8 words each)
-void launch_leaf_hash_lde(Prof& prof, hipStream_t s, const felt* lde, uint32_t cols, uint32_t logB,
-                          uint64_t n, uint32_t* nodes, uint64_t L);
-// leaves of FRI layer: row r = [E[r + k*R] for k < F] -> nodes[R + r]
-void launch_leaf_hash_fri(Prof& prof, hipStream_t s, const felt* E, uint64_t R, uint32_t F, uint32_t* nodes);
-// fused builders: leaves + all levels (nodes[1..2L)) in ceil(log2(L)/9) launches
+// fused builders: leaves + all levels (nodes[1..2L), 8 words each) in ceil(log2(L)/9) launches;
+// leaves L (= n*B) of a coset-major LDE matrix (cols x B x n), or the rows of a FRI layer
+// (row r = [E[r + k*R] for k < F])
 // Optional tree tail: with done (a zeroed per-stream counter) the launch that
 // produces the top subtree roots also finishes the tree in its last block and,
 // with coin_seed, runs the FRI coin step (seed <- H(seed || root), alpha_out,
@@ -144,8 +141,6 @@ void launch_shard_top(Prof& prof, hipStream_t s, const uint32_t* roots, uint32_t
                       const MerkleTail* tail);
 void launch_merkle_from_shards(Prof& prof, hipStream_t s, const uint32_t* recv, uint32_t logB, uint32_t logrr,
                                uint32_t logK, uint32_t* nodes, uint32_t* done = nullptr);
-// internal nodes nodes[1..L) from leaves nodes[L..2L)
-void launch_merkle_tree(Prof& prof, hipStream_t s, uint32_t* nodes, uint64_t L);
 constexpr uint32_t PACK_MAX = 16;
 struct PackArgs {
   const void* src[PACK_MAX];
