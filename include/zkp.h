@@ -56,6 +56,117 @@ typedef enum zkp_air_id {
   ZKP_AIR_TRAINING_UPDATE = 3
 } zkp_air_id;
 
+/* ---- caller-defined AIRs: constraint programs ------------------------------
+ * A zkp_air_program states an AIR as data: the transition constraints as a
+ * straight-line program of field operations that the device runs at every point
+ * of the constraint-evaluation domain (and the host verifier at the OOD point),
+ * periodic columns, and single-row assertions. Its values are concrete for one
+ * instance: constants, assertion steps and assertion values are what `Air::new`
+ * derives from the public inputs. zkp_air_register returns an id (>= 16) that
+ * every entry point taking a zkp_air_id accepts; `pub_elems` still seeds the
+ * coin there, the program itself never reads it.
+ *
+ * Op encoding (one uint64_t per op):
+ *   bits  0..7   opcode (ZKP_OP_*)
+ *   bits  8..15  destination register (ADD, SUB, MUL; 0 for EMIT)
+ *   bits 16..31  operand a
+ *   bits 32..47  operand b (ADD, SUB, MUL; 0 for EMIT)
+ *   bits 48..63  zero
+ * An operand is (kind << 13) | index with kind one of ZKP_SRC_*:
+ *   REG index < num_registers, CUR / NEXT index < width (the frame's two rows),
+ *   PERIODIC index < num_periodic, CONST index < num_constants.
+ * ADD / SUB / MUL write registers[dst] = a op b; EMIT a yields the value of the
+ * next transition constraint, in order (exactly num_constraints EMITs). A register
+ * must be written before it is read.
+ *
+ * degrees[i] (1..17) is constraint i's declared degree in trace-column factors
+ * (winterfell `TransitionConstraintDegree::new`); the AIR's constraint-evaluation
+ * blowup comes from the largest one. Registration walks the code (ADD/SUB -> max,
+ * MUL -> sum, periodic values and constants -> 0) and refuses a constraint whose
+ * syntactic degree exceeds its declared degree.
+ * Periodic column p holds periodic_cycles[p] values (a power of two in 2..1024,
+ * at most the trace length it is used with), all columns' values concatenated in
+ * periodic_values. Assertions are single-row (`Assertion::single`), over at most
+ * 4 distinct steps; they are kept sorted by (step, column), the order in which
+ * winterfell draws their composition coefficients, so a caller may pass them in
+ * any order. */
+enum { ZKP_OP_ADD = 0, ZKP_OP_SUB = 1, ZKP_OP_MUL = 2, ZKP_OP_EMIT = 3 };
+enum { ZKP_SRC_REG = 0, ZKP_SRC_CUR = 1, ZKP_SRC_NEXT = 2, ZKP_SRC_PERIODIC = 3, ZKP_SRC_CONST = 4 };
+#define ZKP_AIR_OPERAND(kind, index) ((uint64_t)(((uint32_t)(kind) << 13) | (uint32_t)(index)))
+#define ZKP_AIR_OP(opcode, dst, a, b) \
+  ((uint64_t)(opcode) | ((uint64_t)(dst) << 8) | ((uint64_t)(a) << 16) | ((uint64_t)(b) << 32))
+enum {
+  ZKP_AIR_FIRST_ID = 16,         /* registered ids start here */
+  ZKP_AIR_MAX_CONSTRAINTS = 1024,
+  ZKP_AIR_MAX_DEGREE = 17,
+  ZKP_AIR_MAX_CONSTANTS = 256,
+  ZKP_AIR_MAX_PERIODIC = 8,
+  ZKP_AIR_MAX_CYCLE = 1024,
+  ZKP_AIR_MAX_ASSERTIONS = 1024,
+  ZKP_AIR_MAX_ASSERTION_STEPS = 4,
+  ZKP_AIR_MAX_OPS = 8192,
+  ZKP_AIR_MAX_REGISTERS = 32
+};
+typedef struct zkp_air_assertion {
+  uint32_t column;
+  uint32_t reserved;  /* 0 */
+  uint64_t step;
+  zkp_felt value;
+} zkp_air_assertion;
+typedef struct zkp_air_program {
+  uint32_t width;                      /* trace columns, 1..255 */
+  uint32_t num_constraints;            /* 1..1024 */
+  const uint8_t* degrees;              /* num_constraints declared degrees, 1..17 */
+  uint32_t num_constants;              /* <= 256 */
+  const zkp_felt* constants;           /* canonical felts */
+  uint32_t num_periodic;               /* <= 8 */
+  const uint32_t* periodic_cycles;     /* num_periodic cycle lengths */
+  const zkp_felt* periodic_values;     /* sum of the cycles, column after column */
+  uint32_t num_assertions;             /* <= 1024 */
+  const zkp_air_assertion* assertions;
+  uint32_t num_registers;              /* 1..32 */
+  uint32_t num_ops;                    /* 1..8192 */
+  const uint64_t* ops;
+} zkp_air_program;
+/* Validates everything that does not depend on the trace length and stores a copy
+ * in a process-wide table (thread-safe); *air_id receives the new id. Ids are never
+ * reused. ZKP_ERR_ARGUMENT on a refused program: zkp_air_last_error() names the
+ * failing field (per thread, valid until the thread's next zkp_air_* call). */
+int zkp_air_register(const zkp_air_program* program, int* air_id);
+/* Frees the id (ZKP_ERR_ARGUMENT if it is not registered). Sessions and proofs
+ * already running under it keep their copy. */
+int zkp_air_unregister(int air_id);
+const char* zkp_air_last_error(void);
+/* Checks that need the trace length n. A registered id's entry points return
+ * ZKP_ERR_PUB_INPUTS (zkp_verify: ZKP_VERIFY_PUB_INPUTS) for:
+ *  - a width other than the program's;
+ *  - an assertion step >= n;
+ *  - a periodic cycle > n;
+ *  - an n that divides d - 1, d being the largest declared degree (degree 9 over
+ *    8 rows). The quotient of a degree-d constraint has (d-1)(n-1) + 1 coefficients.
+ *    winterfell's count gives ceil((d-1)(n-1)/n) composition columns of n
+ *    coefficients each, which is one coefficient short exactly in that case, so no
+ *    proof of such a shape verifies.
+ * Sharded proving over more than one rank returns ZKP_ERR_UNSUPPORTED_AIR for a
+ * registered id from its arguments alone, before the first collective (the
+ * communicator stays usable); a communicator of one rank accepts it.
+ * Memory: a context keeps the device image of one program (the last id, n and
+ * blowup it evaluated), and one table of n * ce divisor inverses per distinct
+ * (domain, assertion step) it has met, like the built-in ids' tables. Instances
+ * that assert other rows therefore add tables until the context is destroyed. */
+
+/* Host-only trace validation (winterfell's debug-build `validate` of a trace,
+ * which `Prover::prove` runs before proving): every transition constraint on the
+ * rows 0..n-2 with the periodic values of the row, then every assertion. A valid
+ * trace returns ZKP_OK with *bad_row = UINT64_MAX. Otherwise still ZKP_OK, with
+ * either the first failing row and its first failing constraint in *bad_row /
+ * *bad_constraint (*bad_assertion = UINT32_MAX), or, when every transition holds,
+ * *bad_row = the step of the first failing assertion (in stored order) and its
+ * index in *bad_assertion (*bad_constraint = UINT32_MAX). Registered ids only:
+ * the built-in ids return ZKP_ERR_UNSUPPORTED_AIR. */
+int zkp_air_check_trace(int air_id, const zkp_felt* trace_cols, uint32_t width, uint64_t n, uint64_t* bad_row,
+                        uint32_t* bad_constraint, uint32_t* bad_assertion);
+
 /* winterfell `BatchingMethod`. */
 enum { ZKP_BATCHING_LINEAR = 0, ZKP_BATCHING_ALGEBRAIC = 1, ZKP_BATCHING_HORNER = 2 };
 /* winterfell `FieldExtension` (only None is supported, as in the reference). */

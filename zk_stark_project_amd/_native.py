@@ -81,6 +81,7 @@ EXPORTED = [
     "zkp_session_shape",
     "zkp_channel_create", "zkp_channel_destroy", "zkp_channel_commit", "zkp_channel_commit_felts",
     "zkp_channel_draw", "zkp_channel_seed", "zkp_channel_query_positions", "zkp_ctx_trim",
+    "zkp_air_register", "zkp_air_unregister", "zkp_air_last_error", "zkp_air_check_trace",
 ]
 
 # zkp_host_transport callbacks (include/zkp.h)
@@ -113,6 +114,33 @@ class VerifierError(ValueError):
         self.code = code
         self.kind = VERIFY_STATUS.get(code, STATUS.get(code, "unknown"))
         super().__init__(f"proof rejected: {self.kind} (status {code})")
+
+
+
+class AirAssertionC(ctypes.Structure):
+    """`zkp_air_assertion` (include/zkp.h)."""
+    _fields_ = [("column", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("step", ctypes.c_uint64),
+                ("value", Felt)]
+
+
+class AirProgramC(ctypes.Structure):
+    """`zkp_air_program` (include/zkp.h)."""
+    _fields_ = [
+        ("width", ctypes.c_uint32), ("num_constraints", ctypes.c_uint32),
+        ("degrees", ctypes.POINTER(ctypes.c_uint8)),
+        ("num_constants", ctypes.c_uint32), ("constants", ctypes.POINTER(Felt)),
+        ("num_periodic", ctypes.c_uint32), ("periodic_cycles", ctypes.POINTER(ctypes.c_uint32)),
+        ("periodic_values", ctypes.POINTER(Felt)),
+        ("num_assertions", ctypes.c_uint32), ("assertions", ctypes.POINTER(AirAssertionC)),
+        ("num_registers", ctypes.c_uint32), ("num_ops", ctypes.c_uint32),
+        ("ops", ctypes.POINTER(ctypes.c_uint64)),
+    ]
+
+
+def _air(air) -> int:
+    """An AIR id: a built-in id, or an object carrying one (a registered AirProgram, an Air class)."""
+    return int(getattr(air, "AIR_ID", air))
+
 
 _lib = None
 _lock = threading.Lock()
@@ -194,8 +222,64 @@ def load():
         L.zkp_channel_draw.argtypes = [vp, u32, u32, vp]
         L.zkp_channel_seed.argtypes = [vp, ctypes.c_char_p]
         L.zkp_channel_query_positions.argtypes = [vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u32)]
+        L.zkp_air_register.argtypes = [ctypes.POINTER(AirProgramC), ctypes.POINTER(i32)]
+        L.zkp_air_unregister.argtypes = [i32]
+        L.zkp_air_last_error.argtypes = []
+        L.zkp_air_last_error.restype = ctypes.c_char_p
+        L.zkp_air_check_trace.argtypes = [i32, vp, u32, u64, ctypes.POINTER(u64), ctypes.POINTER(u32),
+                                          ctypes.POINTER(u32)]
         _lib = L
         return L
+
+
+def air_register(width: int, degrees, constants, periodic, assertions, num_registers: int, ops) -> int:
+    """zkp_air_register: `periodic` is a list of value lists, `assertions` (column, step, value)
+    triples, `ops` encoded op words. Returns the new id; a refused program raises ZkpError
+    with the failing field in its message."""
+    L = load()
+    mask = 2**64 - 1
+    felts = lambda vals: (Felt * max(1, len(vals)))(*[Felt(int(v) & mask, int(v) >> 64) for v in vals])
+    pc = AirProgramC()
+    pc.width, pc.num_constraints = width, len(degrees)
+    deg = (ctypes.c_uint8 * max(1, len(degrees)))(*degrees)
+    pc.degrees = deg
+    cst = felts(constants)
+    pc.num_constants, pc.constants = len(constants), cst
+    cyc = (ctypes.c_uint32 * max(1, len(periodic)))(*[len(c) for c in periodic])
+    pv = felts([v for c in periodic for v in c])
+    pc.num_periodic, pc.periodic_cycles, pc.periodic_values = len(periodic), cyc, pv
+    asr = (AirAssertionC * max(1, len(assertions)))(
+        *[AirAssertionC(c, 0, s, Felt(int(v) & mask, int(v) >> 64)) for c, s, v in assertions])
+    pc.num_assertions, pc.assertions = len(assertions), asr
+    opw = (ctypes.c_uint64 * max(1, len(ops)))(*ops)
+    pc.num_registers, pc.num_ops, pc.ops = num_registers, len(ops), opw
+    out = ctypes.c_int()
+    rc = L.zkp_air_register(ctypes.byref(pc), ctypes.byref(out))
+    if rc:
+        raise ZkpError(rc, "zkp_air_register: " + (L.zkp_air_last_error() or b"").decode(errors="replace"))
+    return out.value
+
+
+def air_unregister(air_id: int) -> None:
+    rc = load().zkp_air_unregister(int(air_id))
+    if rc:
+        raise ZkpError(rc, "zkp_air_unregister")
+
+
+def air_check_trace(air, trace: np.ndarray):
+    """zkp_air_check_trace on a (width, n, 2) uint64 column-major trace: None for a valid
+    trace, else (row, constraint, assertion) with None for the part that does not apply."""
+    L = load()
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    row, con, asr = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()
+    rc = L.zkp_air_check_trace(_air(air), trace.ctypes.data, int(trace.shape[0]), int(trace.shape[1]),
+                               ctypes.byref(row), ctypes.byref(con), ctypes.byref(asr))
+    if rc:
+        raise ZkpError(rc, "zkp_air_check_trace")
+    if row.value == 2**64 - 1:
+        return None
+    none = 2**32 - 1
+    return (row.value, None if con.value == none else con.value, None if asr.value == none else asr.value)
 
 
 def mimc_trace(seed: int, n: int) -> np.ndarray:
@@ -212,7 +296,7 @@ def verify_status(air_id: int, proof: bytes, pub, options: ProofOptions) -> int:
     """zkp_verify (host-only, no device): 0 or a zkp_verify_status code."""
     L = load()
     pub_np = np.array([[v & (2**64 - 1), v >> 64] for v in pub], dtype=np.uint64).reshape(-1, 2)
-    return L.zkp_verify(int(air_id), bytes(proof), len(proof), pub_np.ctypes.data if len(pub) else None,
+    return L.zkp_verify(_air(air_id), bytes(proof), len(proof), pub_np.ctypes.data if len(pub) else None,
                         len(pub), ctypes.byref(options.to_c()))
 
 
@@ -341,6 +425,7 @@ class Context:
     def prove(self, air_id: int, trace: np.ndarray, pub, options: ProofOptions, device_ptr=None):
         """trace: (width, n, 2) uint64 host array (ignored when device_ptr is given)."""
         w, n = int(trace.shape[0]), int(trace.shape[1])
+        air_id = _air(air_id)
         pubb = b"".join(int(v).to_bytes(16, "little") for v in pub)
         out = ctypes.POINTER(ctypes.c_uint8)()
         olen = ctypes.c_uint64()
@@ -362,6 +447,7 @@ class Context:
     def prove_sharded(self, comm: "Comm", air_id: int, trace, pub, options: ProofOptions, shape=None):
         """One rank of a coset-sharded proof (collective over `comm`). `trace` is a
         (width, n, 2) uint64 host array, or a device pointer with shape=(width, n)."""
+        air_id = _air(air_id)
         pubb = b"".join(int(v).to_bytes(16, "little") for v in pub)
         out = ctypes.POINTER(ctypes.c_uint8)()
         olen = ctypes.c_uint64()
@@ -536,7 +622,7 @@ class Session:
         self.ptr = ctypes.c_void_p()
         self._pub = _felts(pub) if len(pub) else None
         self._opts = options.to_c()
-        ctx._check(self.lib.zkp_session_create(ctx.ptr, air_id, width, n,
+        ctx._check(self.lib.zkp_session_create(ctx.ptr, _air(air_id), width, n,
                                                self._pub.ctypes.data if self._pub is not None else None,
                                                len(pub), ctypes.byref(self._opts), ctypes.byref(self.ptr)),
                    "zkp_session_create")
@@ -636,7 +722,7 @@ class Channel:
         self.options = options
         self.ptr = ctypes.c_void_p()
         pb = _felts(pub) if len(pub) else None
-        rc = self.lib.zkp_channel_create(air_id, width, n, pb.ctypes.data if pb is not None else None, len(pub),
+        rc = self.lib.zkp_channel_create(_air(air_id), width, n, pb.ctypes.data if pb is not None else None, len(pub),
                                          ctypes.byref(options.to_c()), ctypes.byref(self.ptr))
         if rc:
             raise ZkpError(rc, "zkp_channel_create")

@@ -172,3 +172,283 @@ class TrainingUpdateAir:
         out = [Assertion(i, 0, self.pub_inputs.initial_masked[i]) for i in range(half)]
         out += [Assertion(i, last, self.pub_inputs.final_masked[i]) for i in range(half)]
         return out
+
+
+# ------------------------------------------------------- caller-defined AIRs
+# A constraint program (include/zkp.h `zkp_air_program`): the transition constraints
+# as a straight-line program of field operations that the device runs at every point
+# of the constraint-evaluation domain, periodic columns, and single-row assertions.
+OP_ADD, OP_SUB, OP_MUL, OP_EMIT = 0, 1, 2, 3
+SRC_REG, SRC_CUR, SRC_NEXT, SRC_PERIODIC, SRC_CONST = 0, 1, 2, 3, 4
+MAX_REGISTERS, MAX_OPS = 32, 8192
+
+
+class Expr:
+    """A node of an AirProgram's expression graph (`+ - *`, `** k` for small k)."""
+    __slots__ = ("prog", "id", "kind", "a", "b")
+
+    def __init__(self, prog, id_, kind, a, b):
+        self.prog, self.id, self.kind, self.a, self.b = prog, id_, kind, a, b
+
+    def _other(self, o):
+        if isinstance(o, Expr):
+            if o.prog is not self.prog:
+                raise ValueError("expressions of two different programs")
+            return o
+        return self.prog.const(o)
+
+    def __add__(self, o):
+        return self.prog._op("add", self, self._other(o))
+
+    def __radd__(self, o):
+        return self.prog._op("add", self._other(o), self)
+
+    def __sub__(self, o):
+        return self.prog._op("sub", self, self._other(o))
+
+    def __rsub__(self, o):
+        return self.prog._op("sub", self._other(o), self)
+
+    def __mul__(self, o):
+        return self.prog._op("mul", self, self._other(o))
+
+    def __rmul__(self, o):
+        return self.prog._op("mul", self._other(o), self)
+
+    def __neg__(self):
+        return self.prog._op("sub", self.prog.const(0), self)
+
+    def __pow__(self, k):
+        if not isinstance(k, int) or k < 1 or k > 64:
+            raise ValueError("power must be an integer in 1..64")
+        out, base = None, self
+        while k:  # square and multiply
+            if k & 1:
+                out = base if out is None else out * base
+            k >>= 1
+            if k:
+                base = base * base
+        return out
+
+
+class _Columns:
+    def __init__(self, prog, kind):
+        self.prog, self.kind = prog, kind
+
+    def __getitem__(self, c):
+        c = int(c)
+        if not 0 <= c < self.prog.width:
+            raise IndexError(f"column {c} outside the trace width {self.prog.width}")
+        return self.prog._leaf(self.kind, c)
+
+
+class CompiledProgram:
+    """The op stream of an AirProgram after register allocation."""
+
+    def __init__(self, ops, num_registers):
+        self.ops, self.num_registers = ops, num_registers
+
+
+class RegisteredAir:
+    """A registered constraint program: `.AIR_ID` is accepted wherever a built-in id is
+    (Context.prove, prove_device, verify, verify_status, Session, Channel,
+    prove_by_stages). The id is freed by close() or when the object is collected."""
+
+    def __init__(self, air_id, program):
+        self.AIR_ID = air_id
+        self.WIDTH = program.width
+        self.num_constraints = len(program.constraints)
+        self.num_assertions = len(program.assertions)
+        self.num_coeffs = self.num_constraints + self.num_assertions  # composition coefficients
+
+    def __int__(self):
+        return self.AIR_ID
+
+    __index__ = __int__
+
+    def check_trace(self, trace):
+        from . import _native
+        return _native.air_check_trace(self.AIR_ID, trace)
+
+    def close(self):
+        if self.AIR_ID is not None:
+            from . import _native
+            aid, self.AIR_ID = self.AIR_ID, None
+            _native.air_unregister(aid)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AirProgram:
+    """Builder of a constraint program over a trace of `width` columns.
+
+        p = AirProgram(1)
+        K = p.periodic([(j + 1) * 10**6 for j in range(64)])
+        p.constraint(p.next[0] - (p.cur[0] + K) ** 7, degree=7)
+        p.assertion(0, 0, seed); p.assertion(0, n - 1, result)
+        air = p.register()          # air.AIR_ID
+
+    Values are concrete for one instance (what `Air::new` derives from the public
+    inputs). Equal subexpressions are shared; registers are allocated by a linear scan
+    over last uses. evaluate() is a pure-Python evaluation of the same constraints."""
+
+    def __init__(self, width: int):
+        self.width = int(width)
+        self.cur, self.next = _Columns(self, "cur"), _Columns(self, "next")
+        self._nodes = []       # creation order = a topological order
+        self._intern = {}
+        self.constants = []    # the constant pool
+        self._const_index = {}
+        self.periodic_columns = []
+        self.constraints = []  # (Expr, degree)
+        self.assertions = []   # (column, step, value)
+
+    # -- expression nodes
+    def _leaf(self, kind, index):
+        key = (kind, index)
+        if key not in self._intern:
+            self._intern[key] = Expr(self, len(self._nodes), kind, index, None)
+            self._nodes.append(self._intern[key])
+        return self._intern[key]
+
+    def _op(self, kind, a, b):
+        if kind in ("add", "mul") and b.id < a.id:
+            a, b = b, a  # commutative: one node for x*y and y*x
+        key = (kind, a.id, b.id)
+        if key not in self._intern:
+            self._intern[key] = Expr(self, len(self._nodes), kind, a, b)
+            self._nodes.append(self._intern[key])
+        return self._intern[key]
+
+    def const(self, v) -> Expr:
+        v = int(v) % P
+        if v not in self._const_index:
+            self._const_index[v] = len(self.constants)
+            self.constants.append(v)
+        return self._leaf("const", self._const_index[v])
+
+    def periodic(self, values) -> Expr:
+        """A periodic column: `values` repeats along the trace (a power-of-two cycle in 2..1024)."""
+        self.periodic_columns.append([int(v) % P for v in values])
+        return self._leaf("periodic", len(self.periodic_columns) - 1)
+
+    def constraint(self, expr, degree: int):
+        """A transition constraint `expr == 0` on every row but the last; `degree` is its
+        declared degree in trace-column factors (TransitionConstraintDegree::new)."""
+        if not isinstance(expr, Expr):
+            expr = self.const(expr)
+        self.constraints.append((expr, int(degree)))
+
+    def assertion(self, column: int, step: int, value: int):
+        """`Assertion::single(column, step, value)`."""
+        self.assertions.append((int(column), int(step), int(value) % P))
+
+    def sorted_assertions(self):
+        """The assertions in the order their composition coefficients are drawn: (step, column)."""
+        return sorted(self.assertions, key=lambda a: (a[1], a[0]))
+
+    # -- the spec
+    def evaluate(self, cur_row, next_row, row_index: int = 0, periodic=None):
+        """Every constraint's value on the frame (cur_row, next_row) at trace row `row_index`
+        (periodic columns take values[row_index % cycle]); big-int arithmetic mod P. Off the
+        trace domain, `periodic` gives the periodic columns' values at the frame's point."""
+        per = list(periodic) if periodic is not None else [c[row_index % len(c)] for c in self.periodic_columns]
+        return self._evaluate(cur_row, next_row, per)
+
+    def _evaluate(self, cur_row, next_row, per):
+        val = [0] * len(self._nodes)
+        for nd in self._nodes:
+            if nd.kind == "cur":
+                v = int(cur_row[nd.a])
+            elif nd.kind == "next":
+                v = int(next_row[nd.a])
+            elif nd.kind == "periodic":
+                v = per[nd.a]
+            elif nd.kind == "const":
+                v = self.constants[nd.a]
+            elif nd.kind == "add":
+                v = val[nd.a.id] + val[nd.b.id]
+            elif nd.kind == "sub":
+                v = val[nd.a.id] - val[nd.b.id]
+            else:
+                v = val[nd.a.id] * val[nd.b.id]
+            val[nd.id] = v % P
+        return [val[e.id] for e, _ in self.constraints]
+
+    # -- code generation
+    def compile(self) -> CompiledProgram:
+        """Ops in dependency order, each constraint's EMIT right after its value; registers
+        from a linear scan over last uses (a register is free again after its last read)."""
+        leaf = {"cur": SRC_CUR, "next": SRC_NEXT, "periodic": SRC_PERIODIC, "const": SRC_CONST}
+        code = {"add": OP_ADD, "sub": OP_SUB, "mul": OP_MUL}
+        order, placed = [], set()   # ("op", node) / ("emit", node)
+        for root, _ in self.constraints:
+            stack = [(root, False)]
+            while stack:
+                nd, done = stack.pop()
+                if nd.kind in leaf or nd.id in placed:
+                    continue
+                if done:
+                    placed.add(nd.id)
+                    order.append(("op", nd))
+                else:
+                    stack.append((nd, True))
+                    stack.append((nd.b, False))
+                    stack.append((nd.a, False))
+            order.append(("emit", root))
+        last_use = {}
+        for i, (what, nd) in enumerate(order):
+            for src in ((nd,) if what == "emit" else (nd.a, nd.b)):
+                if src.kind not in leaf:
+                    last_use[src.id] = i
+        free = list(range(MAX_REGISTERS - 1, -1, -1))
+        reg, used, ops = {}, 0, []
+
+        def operand(src):
+            if src.kind in leaf:
+                return (leaf[src.kind] << 13) | src.a
+            return (SRC_REG << 13) | reg[src.id]
+        for i, (what, nd) in enumerate(order):
+            srcs = (nd,) if what == "emit" else (nd.a, nd.b)
+            enc = [operand(s) for s in srcs]
+            for s in set(x.id for x in srcs if x.kind not in leaf):
+                if last_use[s] == i:
+                    free.append(reg.pop(s))
+            if what == "emit":
+                ops.append(OP_EMIT | (enc[0] << 16))
+                continue
+            if nd.id not in last_use:
+                continue  # (unreachable: every placed op feeds an op or an EMIT)
+            if not free:
+                raise ValueError(f"the program needs more than {MAX_REGISTERS} registers")
+            r = free.pop()
+            reg[nd.id] = r
+            used = max(used, r + 1)
+            ops.append(code[nd.kind] | (r << 8) | (enc[0] << 16) | (enc[1] << 32))
+        if len(ops) > MAX_OPS:
+            raise ValueError(f"the program has {len(ops)} ops, more than {MAX_OPS}")
+        return CompiledProgram(ops, max(used, 1))
+
+    def register(self) -> RegisteredAir:
+        """zkp_air_register: validates the program and returns its id holder."""
+        from . import _native
+        cp = self.compile()
+        aid = _native.air_register(self.width, [d for _, d in self.constraints], self.constants,
+                                   self.periodic_columns, self.assertions, cp.num_registers, cp.ops)
+        return RegisteredAir(aid, self)
+
+    def check_trace(self, trace):
+        """zkp_air_check_trace on a (width, n, 2) uint64 column-major trace: None when every
+        transition and assertion holds, else (row, constraint, assertion)."""
+        with self.register() as air:
+            return air.check_trace(trace)

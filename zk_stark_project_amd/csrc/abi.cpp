@@ -349,6 +349,37 @@ int zkp_kernel_stats_table(zkp_ctx* ctx, char** table) {
   });
 }
 
+// ---- caller-defined AIRs: the table of constraint programs (air_program.hpp). Host-only.
+int zkp_air_register(const zkp_air_program* program, int* air_id) {
+  std::string& err = airp::last_error();
+  err.clear();
+  try {
+    if (!air_id) {
+      err = "air_id: null";
+      return ZKP_ERR_ARGUMENT;
+    }
+    auto p = std::make_shared<airp::Program>();
+    err = airp::validate(program, *p);
+    if (!err.empty()) return ZKP_ERR_ARGUMENT;
+    *air_id = airp::insert(std::move(p));
+    return ZKP_OK;
+  } catch (const std::bad_alloc&) {
+    return ZKP_ERR_OOM;
+  } catch (...) {
+    return ZKP_ERR_ARGUMENT;
+  }
+}
+
+int zkp_air_unregister(int air_id) {
+  std::string& err = airp::last_error();
+  err.clear();
+  if (airp::erase(air_id)) return ZKP_OK;
+  err = "air_id: not a registered id";
+  return ZKP_ERR_ARGUMENT;
+}
+
+const char* zkp_air_last_error(void) { return airp::last_error().c_str(); }
+
 // Host-side MiMC AIR trace builder (trace construction, like TraceTable building
 // in the reference; not part of the proving hot path).
 int zkp_build_mimc_trace(const uint8_t seed[16], uint64_t n, zkp_felt* out) {

@@ -1,0 +1,236 @@
+// air_program.hpp — caller-defined AIRs (include/zkp.h, zkp_air_program): the
+// validated copy of a constraint program, the process-wide table of registered
+// ids, and the host interpreter that the verifier (OOD frame) and
+// zkp_air_check_trace (trace rows) share. The device runs the same op stream in
+// k_eval_program (kernels.hip). Pure host code: no HIP calls.
+#pragma once
+#include <algorithm>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/zkp.h"
+#include "felt.hpp"
+
+namespace airp {
+using namespace fp;
+
+inline uint32_t op_code(uint64_t op) { return (uint32_t)(op & 0xff); }
+inline uint32_t op_dst(uint64_t op) { return (uint32_t)((op >> 8) & 0xff); }
+inline uint32_t op_a(uint64_t op) { return (uint32_t)((op >> 16) & 0xffff); }
+inline uint32_t op_b(uint64_t op) { return (uint32_t)((op >> 32) & 0xffff); }
+inline uint32_t src_kind(uint32_t operand) { return operand >> 13; }
+inline uint32_t src_index(uint32_t operand) { return operand & 0x1fff; }
+
+// a registered program: the caller's arrays copied, the assertions sorted by (step, column)
+struct Program {
+  uint32_t width = 0, num_t = 0, base_degree = 0, nreg = 0;
+  std::vector<uint8_t> degrees;
+  std::vector<felt> consts;
+  std::vector<std::vector<felt>> periodic;  // column p: its cycle of values
+  std::vector<uint32_t> a_col;
+  std::vector<uint64_t> a_step;
+  std::vector<felt> a_val;
+  std::vector<uint64_t> ops;
+  uint32_t max_cycle() const {
+    uint32_t m = 0;
+    for (auto& c : periodic) m = std::max<uint32_t>(m, (uint32_t)c.size());
+    return m;
+  }
+};
+
+// Checks every rule of zkp_air_program that does not depend on the trace length and
+// fills `out`; returns the empty string, or a message naming the failing field.
+inline std::string validate(const zkp_air_program* p, Program& out) {
+  auto idx = [](const char* what, size_t i, const std::string& why) {
+    return std::string(what) + "[" + std::to_string(i) + "]: " + why;
+  };
+  if (!p) return "program: null";
+  if (p->width < 1 || p->width > 255) return "width: must be 1..255";
+  if (p->num_constraints < 1 || p->num_constraints > ZKP_AIR_MAX_CONSTRAINTS) return "num_constraints: must be 1..1024";
+  if (!p->degrees) return "degrees: null";
+  out.width = p->width;
+  out.num_t = p->num_constraints;
+  out.base_degree = 0;
+  out.degrees.assign(p->degrees, p->degrees + p->num_constraints);
+  for (uint32_t i = 0; i < p->num_constraints; i++) {
+    if (p->degrees[i] < 1 || p->degrees[i] > ZKP_AIR_MAX_DEGREE) return idx("degrees", i, "must be 1..17");
+    out.base_degree = std::max<uint32_t>(out.base_degree, p->degrees[i]);
+  }
+  if (p->num_constants > ZKP_AIR_MAX_CONSTANTS) return "num_constants: at most 256";
+  if (p->num_constants && !p->constants) return "constants: null";
+  out.consts.resize(p->num_constants);
+  for (uint32_t i = 0; i < p->num_constants; i++) {
+    out.consts[i] = make(p->constants[i].lo, p->constants[i].hi);
+    if (ge_p(out.consts[i])) return idx("constants", i, "not a canonical field element");
+  }
+  if (p->num_periodic > ZKP_AIR_MAX_PERIODIC) return "num_periodic: at most 8";
+  if (p->num_periodic && (!p->periodic_cycles || !p->periodic_values)) return "periodic_cycles / periodic_values: null";
+  out.periodic.resize(p->num_periodic);
+  size_t off = 0;
+  for (uint32_t c = 0; c < p->num_periodic; c++) {
+    const uint32_t cyc = p->periodic_cycles[c];
+    if (cyc < 2 || cyc > ZKP_AIR_MAX_CYCLE || (cyc & (cyc - 1)))
+      return idx("periodic_cycles", c, "must be a power of two in 2..1024");
+    out.periodic[c].resize(cyc);
+    for (uint32_t j = 0; j < cyc; j++) {
+      const zkp_felt v = p->periodic_values[off + j];
+      out.periodic[c][j] = make(v.lo, v.hi);
+      if (ge_p(out.periodic[c][j])) return idx("periodic_values", off + j, "not a canonical field element");
+    }
+    off += cyc;
+  }
+  if (p->num_assertions > ZKP_AIR_MAX_ASSERTIONS) return "num_assertions: at most 1024";
+  if (p->num_assertions && !p->assertions) return "assertions: null";
+  {
+    std::vector<uint32_t> order(p->num_assertions);
+    for (uint32_t i = 0; i < p->num_assertions; i++) {
+      order[i] = i;
+      const zkp_air_assertion& a = p->assertions[i];
+      if (a.column >= p->width) return idx("assertions", i, "column outside the trace width");
+      if (ge_p(make(a.value.lo, a.value.hi))) return idx("assertions", i, "value not a canonical field element");
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+      const zkp_air_assertion &a = p->assertions[x], &b = p->assertions[y];
+      return a.step != b.step ? a.step < b.step : a.column < b.column;
+    });
+    uint32_t steps = 0;
+    for (uint32_t k = 0; k < p->num_assertions; k++) {
+      const zkp_air_assertion& a = p->assertions[order[k]];
+      if (k && out.a_step.back() == a.step && out.a_col.back() == a.column)
+        return idx("assertions", order[k], "duplicate (column, step)");
+      if (!k || out.a_step.back() != a.step) steps++;
+      if (steps > ZKP_AIR_MAX_ASSERTION_STEPS) return idx("assertions", order[k], "more than 4 distinct steps");
+      out.a_col.push_back(a.column);
+      out.a_step.push_back(a.step);
+      out.a_val.push_back(make(a.value.lo, a.value.hi));
+    }
+  }
+  if (p->num_registers < 1 || p->num_registers > ZKP_AIR_MAX_REGISTERS) return "num_registers: must be 1..32";
+  if (p->num_ops < 1 || p->num_ops > ZKP_AIR_MAX_OPS) return "num_ops: must be 1..8192";
+  if (!p->ops) return "ops: null";
+  out.nreg = p->num_registers;
+  out.ops.assign(p->ops, p->ops + p->num_ops);
+  // the walk: operand ranges, registers written before they are read, the EMIT
+  // count, and each constraint's syntactic degree against its declared one
+  constexpr uint32_t DEG_CAP = 1u << 16;  // saturation (a chain of squarings doubles it per op)
+  uint32_t rdeg[ZKP_AIR_MAX_REGISTERS];
+  bool rset[ZKP_AIR_MAX_REGISTERS] = {};
+  uint32_t emitted = 0;
+  for (uint32_t pc = 0; pc < p->num_ops; pc++) {
+    const uint64_t op = p->ops[pc];
+    std::string err;
+    auto operand = [&](uint32_t o, uint32_t& deg) {
+      const uint32_t k = src_kind(o), i = src_index(o);
+      deg = 0;
+      switch (k) {
+        case ZKP_SRC_REG:
+          if (i >= p->num_registers) err = "register operand outside num_registers";
+          else if (!rset[i]) err = "register read before it is written";
+          else deg = rdeg[i];
+          break;
+        case ZKP_SRC_CUR:
+        case ZKP_SRC_NEXT:
+          if (i >= p->width) err = "trace column outside the width";
+          deg = 1;
+          break;
+        case ZKP_SRC_PERIODIC:
+          if (i >= p->num_periodic) err = "periodic column outside num_periodic";
+          break;
+        case ZKP_SRC_CONST:
+          if (i >= p->num_constants) err = "constant outside num_constants";
+          break;
+        default:
+          err = "unknown operand kind";
+      }
+    };
+    if (op >> 48) return idx("ops", pc, "bits 48..63 must be zero");
+    const uint32_t code = op_code(op);
+    uint32_t da = 0, db = 0;
+    if (code == ZKP_OP_EMIT) {
+      if (op_dst(op) || op_b(op)) return idx("ops", pc, "EMIT takes one operand");
+      operand(op_a(op), da);
+      if (!err.empty()) return idx("ops", pc, err);
+      if (emitted >= p->num_constraints) return idx("ops", pc, "more EMITs than num_constraints");
+      if (da > p->degrees[emitted])
+        return idx("degrees", emitted, "the constraint's degree in the code (" + std::to_string(da) +
+                                           ") exceeds the declared degree");
+      emitted++;
+      continue;
+    }
+    if (code != ZKP_OP_ADD && code != ZKP_OP_SUB && code != ZKP_OP_MUL) return idx("ops", pc, "unknown opcode");
+    operand(op_a(op), da);
+    if (err.empty()) operand(op_b(op), db);
+    if (!err.empty()) return idx("ops", pc, err);
+    const uint32_t dst = op_dst(op);
+    if (dst >= p->num_registers) return idx("ops", pc, "destination register outside num_registers");
+    rdeg[dst] = std::min(DEG_CAP, code == ZKP_OP_MUL ? da + db : std::max(da, db));
+    rset[dst] = true;
+  }
+  if (emitted != p->num_constraints) return "ops: fewer EMITs than num_constraints";
+  return "";
+}
+
+// The program on one frame: out[i] = constraint i (per[p] = periodic column p at the
+// frame's point). The canonical field ops of felt.hpp, as on the device.
+inline void evaluate(const Program& pr, const felt* cur, const felt* nxt, const felt* per, felt* out) {
+  felt reg[ZKP_AIR_MAX_REGISTERS];
+  auto fetch = [&](uint32_t o) {
+    const uint32_t i = src_index(o);
+    switch (src_kind(o)) {
+      case ZKP_SRC_REG: return reg[i];
+      case ZKP_SRC_CUR: return cur[i];
+      case ZKP_SRC_NEXT: return nxt[i];
+      case ZKP_SRC_PERIODIC: return per[i];
+      default: return pr.consts[i];
+    }
+  };
+  uint32_t e = 0;
+  for (uint64_t op : pr.ops) {
+    const felt a = fetch(op_a(op));
+    if (op_code(op) == ZKP_OP_EMIT) {
+      out[e++] = a;
+      continue;
+    }
+    const felt b = fetch(op_b(op));
+    reg[op_dst(op)] = op_code(op) == ZKP_OP_MUL ? mul(a, b) : op_code(op) == ZKP_OP_ADD ? add(a, b) : sub(a, b);
+  }
+}
+
+// ---- the process-wide table (ids from ZKP_AIR_FIRST_ID, never reused)
+struct Registry {
+  std::mutex mu;
+  std::map<int, std::shared_ptr<const Program>> table;
+  int next_id = ZKP_AIR_FIRST_ID;
+};
+inline Registry& registry() {
+  static Registry r;
+  return r;
+}
+inline std::shared_ptr<const Program> lookup(int id) {
+  if (id < ZKP_AIR_FIRST_ID) return nullptr;
+  Registry& r = registry();
+  std::lock_guard<std::mutex> lk(r.mu);
+  auto it = r.table.find(id);
+  return it == r.table.end() ? nullptr : it->second;
+}
+inline int insert(std::shared_ptr<const Program> p) {
+  Registry& r = registry();
+  std::lock_guard<std::mutex> lk(r.mu);
+  const int id = r.next_id++;
+  r.table[id] = std::move(p);
+  return id;
+}
+inline bool erase(int id) {
+  Registry& r = registry();
+  std::lock_guard<std::mutex> lk(r.mu);
+  return r.table.erase(id) != 0;
+}
+inline std::string& last_error() {
+  static thread_local std::string e;
+  return e;
+}
+
+}  // namespace airp

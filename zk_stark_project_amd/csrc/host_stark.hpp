@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/zkp.h"
+#include "air_program.hpp"
 #include "blake3.hpp"
 #include "felt.hpp"
 
@@ -185,6 +186,7 @@ struct AirDesc {
   std::vector<uint64_t> a_step;
   std::vector<felt> a_val;
   felt k;
+  std::shared_ptr<const airp::Program> prog;  // registered ids (zkp_air_register): the constraint program
   uint32_t ce_blowup() const {
     uint32_t v = base_degree - 1, p = 1;
     while (p < v) p <<= 1;
@@ -247,6 +249,24 @@ inline int build_air(AirDesc& a, int id, uint32_t w, uint64_t n, const std::vect
       a.a_col[i] = i; a.a_step[i] = 0; a.a_val[i] = pub[i];
       a.a_col[half + i] = i; a.a_step[half + i] = n - 1; a.a_val[half + i] = pub[half + i];
     }
+    return 0;
+  }
+  if (auto pr = airp::lookup(id)) {
+    // a registered constraint program (air_program.hpp): its values are concrete, pub only seeds the coin
+    if (w != pr->width || pr->max_cycle() > n) return ZKP_ERR_PUB_INPUTS;
+    for (uint64_t s : pr->a_step)
+      if (s >= n) return ZKP_ERR_PUB_INPUTS;
+    // A constraint of degree d over n rows has a quotient of degree (d-1)(n-1), and comp_cols()
+    // (winterfell's count) provides ceil((d-1)(n-1)/n) columns of n coefficients: one short
+    // exactly when n divides d-1. No proof of such a shape verifies.
+    if (pr->base_degree > 1 && (pr->base_degree - 1) % n == 0) return ZKP_ERR_PUB_INPUTS;
+    a.num_t = pr->num_t;
+    a.base_degree = pr->base_degree;
+    a.cycle = 0;
+    a.a_col = pr->a_col;
+    a.a_step = pr->a_step;
+    a.a_val = pr->a_val;
+    a.prog = pr;
     return 0;
   }
   return ZKP_ERR_UNSUPPORTED_AIR;

@@ -385,6 +385,84 @@ __global__ __launch_bounds__(TPB) void k_eval_mimc(EvalCommon c, MimcEvalArgs a,
   });
 }
 
+// A registered constraint program (include/zkp.h zkp_air_program) at one CE point
+// per thread. The op stream, the constants, the coefficients and the assertion
+// tables are the same for every lane: their addresses are built from kernel
+// arguments and loop counters only, so they come through uniform (scalar) loads and
+// the opcode / operand-kind switches are scalar branches. The program's registers
+// live in LDS as [register][thread], 16 bytes per lane and contiguous over the wave
+// (ds_read_b128 / ds_write_b128, one 16-byte slot per lane: conflict-free), sized at
+// launch from the program's register count: PROG_TPB * 16 * nreg bytes per block of
+// one wave. No lane reads another lane's slot, so the kernel has no barrier.
+// Field ops are the canonical add / sub / mul: every value written is canonical.
+constexpr uint32_t PROG_TPB = 64;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
+
+__global__ __launch_bounds__(PROG_TPB) void k_eval_program(EvalCommon c, ProgEvalArgs a, const felt* __restrict__ lde,
+                                                           felt* __restrict__ comp) {
+  extern __shared__ __align__(16) unsigned char prog_lds[];
+  // register r of this lane: rg[r * PROG_TPB]. The pointer keeps its LDS address space, so
+  // a register operand is a ds_read_b128 and never merges with the global loads into a flat one
+  lds_u32x4* const rg = (lds_u32x4*)prog_lds + threadIdx.x;
+  const uint64_t M = (uint64_t)c.cel << c.logn;
+  const uint64_t q = (uint64_t)blockIdx.x * PROG_TPB + threadIdx.x;
+  if (q >= M) return;
+  const CePoint pt = ce_point(c, q);
+  const felt* const cur = lde + pt.off;
+  const felt* const nxt = lde + pt.off_next;
+  auto fetch = [&](uint32_t operand) -> felt {
+    const uint32_t idx = operand & 0x1fff;
+    switch (operand >> 13) {
+      case ZKP_SRC_REG: {
+        const u32x4 r = rg[idx * PROG_TPB];
+        return make((uint64_t)r.x | ((uint64_t)r.y << 32), (uint64_t)r.z | ((uint64_t)r.w << 32));
+      }
+      case ZKP_SRC_CUR: return cur[idx * a.col_stride];
+      case ZKP_SRC_NEXT: return nxt[idx * a.col_stride];
+      case ZKP_SRC_PERIODIC: {
+        const ProgPeriodic d = a.per_desc[idx];
+        return a.per_tab[d.off + ((uint32_t)pt.s & d.mask)];
+      }
+      default: return a.consts[idx];
+    }
+  };
+  // transition part: T = sum_i cc[i] * t_i (an EMIT is a product with its coefficient)
+  felt T = zero();
+  uint32_t emitted = 0;
+  for (uint32_t pc = 0; pc < a.nops; pc++) {
+    const uint64_t op = a.ops[pc];
+    const uint32_t code = (uint32_t)op & 0xff;
+    const felt x = fetch((uint32_t)(op >> 16) & 0xffff);
+    const felt y = code == ZKP_OP_EMIT ? a.cc[emitted] : fetch((uint32_t)(op >> 32) & 0xffff);
+    felt r;
+    if (code == ZKP_OP_ADD) r = add(x, y);
+    else if (code == ZKP_OP_SUB) r = sub(x, y);
+    else r = mul(x, y);
+    if (code == ZKP_OP_EMIT) {
+      T = add(T, r);
+      emitted++;
+    } else {
+      u32x4 w;
+      w.x = (uint32_t)r.lo; w.y = (uint32_t)(r.lo >> 32); w.z = (uint32_t)r.hi; w.w = (uint32_t)(r.hi >> 32);
+      rg[((uint32_t)(op >> 8) & 0xff) * PROG_TPB] = w;
+    }
+  }
+  const felt px = point_x(c.pm, q);
+  felt v = mul(mul(T, sub(px, c.w_last)), c.zinv[pt.u]);
+  // boundary part, one divisor table per group of assertions that share a step
+  const felt* const bcc = a.cc + a.num_t;
+  uint32_t k = 0;
+  static_for<0, (int)PROG_MAX_GROUPS>([&](auto g) {
+    if ((uint32_t)g < a.ngroups) {
+      felt s = zero();
+      for (; k < a.grp_end[g]; k++) s = add(s, mul(bcc[k], sub(cur[a.a_col[k] * a.col_stride], a.a_val[k])));
+      v = add(v, mul(s, a.dinv[g][q]));
+    }
+  });
+  comp[q] = v;
+}
+
 // Linear AIRs. TRANS: transition sum_c a_c*next_c + b_c*cur_c divided by Z_T
 // (GlobalUpdate); without it the transition part is identically zero
 // (TrainingUpdate). Boundary: group 0 = sum_c beta0_c*cur_c - bconst0
@@ -1284,6 +1362,19 @@ void launch_eval_mimc(Prof& prof, hipStream_t s, const EvalCommon& c, const Mimc
   LAUNCH(prof, "eval_mimc", s, (double)M * 48.0,
          hipLaunchKernelGGL(k_eval_mimc, dim3(blocks_for((M + EVAL_CH - 1) / EVAL_CH)), dim3(TPB), 0, s, c, a, lde,
                             a.dinv, comp));
+}
+
+void launch_eval_program(Prof& prof, hipStream_t s, const EvalCommon& c, const ProgEvalArgs& a, const felt* lde,
+                         felt* comp) {
+  const uint64_t M = (uint64_t)c.cel << c.logn;
+  if (a.nreg == 0 || a.nreg > ZKP_AIR_MAX_REGISTERS || a.ngroups > PROG_MAX_GROUPS)
+    launch_fail(ZKP_ERR_ARGUMENT, "constraint program outside the kernel's limits");
+  for (uint32_t g = 0; g < a.ngroups; g++)
+    if (!a.dinv_ready[g]) launch_den_table(prof, s, c.pm, M, a.w_step[g], zero(), 0, a.binv, a.dinv[g]);
+  // LDS: the program's registers, [register][thread] (16 bytes per lane)
+  const size_t lds = (size_t)a.nreg * PROG_TPB * sizeof(felt);
+  LAUNCH(prof, "eval_program", s, (double)M * 48.0,
+         hipLaunchKernelGGL(k_eval_program, dim3(blocks_for(M, PROG_TPB)), dim3(PROG_TPB), lds, s, c, a, lde, comp));
 }
 
 void launch_eval_linear(Prof& prof, hipStream_t s, const EvalCommon& c, const LinearEvalArgs& a, const felt* lde,

@@ -82,7 +82,7 @@ void ProofRun::setup() {
       sw[i] = (uint32_t)coin.seed[4 * i] | ((uint32_t)coin.seed[4 * i + 1] << 8) |
               ((uint32_t)coin.seed[4 * i + 2] << 16) | ((uint32_t)coin.seed[4 * i + 3] << 24);
     ctx->upload(dt_seed, sw, 32);
-    ctx->upload(dt_aval, air.a_val.data(), air.a_val.size() * 16);
+    if (!air.a_val.empty()) ctx->upload(dt_aval, air.a_val.data(), air.a_val.size() * 16);  // a program may assert nothing
   }
   ctx->stage_end("0a_seed");
   ctx->ensure_coset(logn, logB, logce);

@@ -232,6 +232,10 @@ namespace {
 bool sharded_factor_refused(const zkp_comm* comm, const zkp_proof_options* o) {
   return comm && o && comm->world > 1 && check_options(o) == 0 && o->fri_folding_factor != 16;
 }
+// A registered constraint program (zkp_air_register) evaluates pointwise on one
+// rank's CE cosets with no exchange step of its own: a group of more than one rank
+// refuses it the same way, from the arguments alone and before the first collective.
+bool sharded_air_refused(const zkp_comm* comm, int air) { return comm && comm->world > 1 && air >= ZKP_AIR_FIRST_ID; }
 }  // namespace
 
 extern "C" {
@@ -239,6 +243,7 @@ extern "C" {
 int zkp_prove_sharded(zkp_ctx* ctx, zkp_comm* comm, zkp_air_id air, const zkp_felt* trace, uint32_t width,
                       uint64_t n, const zkp_felt* pub, uint64_t n_pub, const zkp_proof_options* opts, uint8_t** proof,
                       uint64_t* proof_len, zkp_transcript* transcript) {
+  if (ctx && sharded_air_refused(comm, air)) return ZKP_ERR_UNSUPPORTED_AIR;
   if (ctx && sharded_factor_refused(comm, opts)) return ZKP_ERR_INVALID_OPTIONS;
   int rc = guarded(ctx, [&] {
     ctx->err.clear();
@@ -256,6 +261,7 @@ int zkp_prove_sharded(zkp_ctx* ctx, zkp_comm* comm, zkp_air_id air, const zkp_fe
 int zkp_prove_sharded_device(zkp_ctx* ctx, zkp_comm* comm, zkp_air_id air, const void* d_trace, uint32_t width,
                              uint64_t n, const zkp_felt* pub, uint64_t n_pub, const zkp_proof_options* opts,
                              uint8_t** proof, uint64_t* proof_len, zkp_transcript* transcript) {
+  if (ctx && sharded_air_refused(comm, air)) return ZKP_ERR_UNSUPPORTED_AIR;
   if (ctx && sharded_factor_refused(comm, opts)) return ZKP_ERR_INVALID_OPTIONS;
   int rc = guarded(ctx, [&] {
     ctx->err.clear();

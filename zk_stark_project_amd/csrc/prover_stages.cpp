@@ -150,6 +150,77 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
   }
   felt* dz = ctx->buf<felt>(zkey, ce);
   if (!ctx->have_cached(zkey)) ctx->upload(dz, zinv.data(), ce * 16);
+  const std::string dom = std::to_string(logn) + "_" + std::to_string(logB) + "_" + std::to_string(u0) + "_" +
+                          std::to_string(cel);
+  if (air.prog) {
+    // a registered constraint program: k_eval_program reads the coefficients from dt_cc as drawn
+    if (!cel) return;
+    const airp::Program& pr = *air.prog;
+    // the program's device image, in 16-byte units: [ops | constants | assertion columns |
+    // periodic descriptors | periodic tables]. A context keeps one image, the last
+    // (id, n, ce) it evaluated (ids are never reused): proving another instance replaces it,
+    // so registering and freeing ids does not grow the context.
+    // Periodic column of cycle c over the CE domain: interpolate over <w_c>, evaluate at
+    // g^(n/c) * <w_{c ce}> (as kper_* below), indexed by the CE index mod c*ce.
+    const size_t P = pr.periodic.size();
+    const size_t o_ops = 0, o_const = o_ops + (pr.ops.size() + 1) / 2, o_col = o_const + pr.consts.size(),
+                 o_desc = o_col + (pr.a_col.size() + 3) / 4, o_tab = o_desc + (P + 1) / 2;
+    size_t total = o_tab;
+    for (const auto& col : pr.periodic) total += col.size() * ce;
+    felt* dimg = ctx->buf<felt>("prog_image", total);
+    std::vector<felt>& img = ctx->host_cache["prog_image"];  // kept: a large image is copied from it asynchronously
+    std::vector<felt>& tag = ctx->host_cache["prog_image_tag"];
+    const felt want[2] = {make((uint64_t)air.id, logn), make(logce, total)};
+    if (tag.size() != 2 || !eq(tag[0], want[0]) || !eq(tag[1], want[1])) {
+      tag.clear();
+      img.assign(total, zero());
+      memcpy(img.data() + o_ops, pr.ops.data(), pr.ops.size() * 8);
+      if (!pr.consts.empty()) memcpy(img.data() + o_const, pr.consts.data(), pr.consts.size() * 16);
+      if (!pr.a_col.empty()) memcpy(img.data() + o_col, pr.a_col.data(), pr.a_col.size() * 4);
+      ProgPeriodic* desc = reinterpret_cast<ProgPeriodic*>(img.data() + o_desc);
+      size_t off = 0;
+      for (size_t p = 0; p < P; p++) {
+        const size_t cyc = pr.periodic[p].size();
+        std::vector<felt> kc = pr.periodic[p];
+        host_interpolate(kc, one());
+        const std::vector<felt> kv = host_evaluate(kc, cyc * ce, pow_u64(g, n / cyc));
+        memcpy(img.data() + o_tab + off, kv.data(), kv.size() * 16);
+        desc[p] = ProgPeriodic{(uint32_t)off, (uint32_t)(cyc * ce - 1)};
+        off += kv.size();
+      }
+      ctx->upload(dimg, img.data(), total * 16);
+      tag.assign(want, want + 2);
+    }
+    ec.zinv = dz;
+    ProgEvalArgs pa{};
+    pa.ops = reinterpret_cast<const uint64_t*>(dimg + o_ops);
+    pa.nops = (uint32_t)pr.ops.size();
+    pa.nreg = pr.nreg;
+    pa.num_t = pr.num_t;
+    pa.consts = dimg + o_const;
+    pa.a_col = reinterpret_cast<const uint32_t*>(dimg + o_col);
+    pa.per_desc = reinterpret_cast<const ProgPeriodic*>(dimg + o_desc);
+    pa.per_tab = dimg + o_tab;
+    pa.cc = dt_cc;
+    pa.a_val = dt_aval;
+    pa.col_stride = n << logBl;
+    pa.binv = ctx->buf<felt>("binv_scratch", ((uint64_t)cel * n) / 2048 + 1);
+    // groups of assertions that share a step (sorted by step): one divisor table
+    // 1/(x - w^step) each, domain-only, cached per (domain, step)
+    for (size_t k = 0; k < air.a_step.size(); k++) {
+      if (k == 0 || air.a_step[k] != air.a_step[k - 1]) {
+        if (pa.ngroups == PROG_MAX_GROUPS) throw ZkpFail{ZKP_ERR_UNSUPPORTED_AIR, "assertions over more than 4 steps"};
+        const uint32_t gi = pa.ngroups++;
+        const std::string key = "binv_prog_" + dom + "_" + std::to_string(air.a_step[k]);
+        pa.w_step[gi] = pow_u64(wn, air.a_step[k]);
+        pa.dinv_ready[gi] = ctx->have_cached(key);
+        pa.dinv[gi] = ctx->buf<felt>(key, (uint64_t)cel * n);
+      }
+      pa.grp_end[pa.ngroups - 1] = (uint32_t)k + 1;
+    }
+    launch_eval_program(pf, st, ec, pa, tlde, comp);
+    return;
+  }
   // coefficient-dependent constants, built on the device from the drawn coefficients
   // (MiMC: Z_T constants with the transition coefficient folded in, then b0, b1;
   // linear AIRs: the 4 coefficient rows + the two boundary sums)
@@ -157,8 +228,6 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
   felt* dconst = ctx->buf<felt>("eval_consts", air.id == ZKP_AIR_MIMC ? (size_t)ce + 4 : 4 * (size_t)lw + 2);
   launch_dt_eval_consts(pf, st, air.id, dt_cc, air.k, ec.w_last, dt_aval, dz, ce, w, air.num_t, dconst);
   ec.zinv = air.id == ZKP_AIR_MIMC ? dconst : dz;
-  const std::string dom = std::to_string(logn) + "_" + std::to_string(logB) + "_" + std::to_string(u0) + "_" +
-                          std::to_string(cel);
   // coefficient form for the linear AIRs (profiles/r03_ab_linear_coef_eval.txt)
   const bool coef_form = air.id != ZKP_AIR_MIMC && coef;
   if (!cel && !coef_form) return;

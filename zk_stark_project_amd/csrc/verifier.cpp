@@ -188,10 +188,21 @@ felt periodic_at(const AirDesc& a, felt x) {
   return horner(c, pow_u64(x, a.n / a.cycle));
 }
 
-// Air::evaluate_transition at the OOD frame
-std::vector<felt> eval_transition(const AirDesc& a, const felt* cur, const felt* nxt, felt kper) {
+// periodic column of `cycle` values at x for a trace of n rows: p(x^(n/cycle)), p interpolated over <w_cycle>
+felt periodic_column_at(std::vector<felt> c, uint64_t n, felt x) {
+  const uint64_t cycle = c.size();
+  host_interpolate(c, one());
+  return horner(c, pow_u64(x, n / cycle));
+}
+
+// Air::evaluate_transition at the OOD frame (z = the frame's point, for a program's periodic columns)
+std::vector<felt> eval_transition(const AirDesc& a, const felt* cur, const felt* nxt, felt kper, felt z) {
   std::vector<felt> out(a.num_t, zero());
-  if (a.id == ZKP_AIR_MIMC) {
+  if (a.prog) {
+    std::vector<felt> per;
+    for (const auto& col : a.prog->periodic) per.push_back(periodic_column_at(col, a.n, z));
+    airp::evaluate(*a.prog, cur, nxt, per.data(), out.data());
+  } else if (a.id == ZKP_AIR_MIMC) {
     felt t = add(cur[0], kper);
     felt t2 = sqr(t), t3 = mul(t2, t), t6 = sqr(t3);
     out[0] = sub(nxt[0], mul(t6, t));
@@ -288,7 +299,7 @@ int verify_impl(int air_id, const uint8_t* proof, uint64_t len, const zkp_felt* 
 
   // ---- 3. OOD consistency (DefaultConstraintEvaluator at z vs the composition columns)
   {
-    std::vector<felt> ev = eval_transition(air, ood_trace.data(), ood_trace.data() + w, periodic_at(air, z));
+    std::vector<felt> ev = eval_transition(air, ood_trace.data(), ood_trace.data() + w, periodic_at(air, z), z);
     felt t = zero();
     for (uint32_t i = 0; i < air.num_t; i++) t = add(t, mul(cc[i], ev[i]));
     const felt zn = pow_u64(z, n);
@@ -410,5 +421,58 @@ extern "C" int zkp_verify(zkp_air_id air, const uint8_t* proof, uint64_t proof_l
     return ZKP_VERIFY_RANDOM_COIN;  // the coin failed to draw a field element
   } catch (...) {
     return ZKP_VERIFY_DESERIALIZATION;
+  }
+}
+
+// Host trace validation for a registered constraint program (include/zkp.h): the
+// interpreter of air_program.hpp on every frame (rows r, r+1; periodic column p at
+// row r is its value r mod cycle), then the assertions in their stored order.
+extern "C" int zkp_air_check_trace(int air_id, const zkp_felt* trace_cols, uint32_t width, uint64_t n,
+                                   uint64_t* bad_row, uint32_t* bad_constraint, uint32_t* bad_assertion) {
+  if (!trace_cols || !bad_row || !bad_constraint || !bad_assertion) return ZKP_ERR_ARGUMENT;
+  if (air_id == ZKP_AIR_MIMC || air_id == ZKP_AIR_GLOBAL_UPDATE || air_id == ZKP_AIR_TRAINING_UPDATE)
+    return ZKP_ERR_UNSUPPORTED_AIR;
+  if (n < 8 || (n & (n - 1)) || width == 0 || width > 255) return ZKP_ERR_TRACE_SHAPE;
+  try {
+    AirDesc air;
+    const int rc = build_air(air, air_id, width, n, {});
+    if (rc) return rc;
+    const airp::Program& pr = *air.prog;
+    *bad_row = UINT64_MAX;
+    *bad_constraint = UINT32_MAX;
+    *bad_assertion = UINT32_MAX;
+    std::vector<felt> cur(width), nxt(width), per(pr.periodic.size()), out(pr.num_t);
+    auto row = [&](uint64_t r, std::vector<felt>& v) {
+      for (uint32_t c = 0; c < width; c++) {
+        const zkp_felt e = trace_cols[(size_t)c * n + r];
+        v[c] = make(e.lo, e.hi);
+      }
+    };
+    row(0, nxt);
+    for (uint64_t r = 0; r + 1 < n; r++) {
+      cur.swap(nxt);
+      row(r + 1, nxt);
+      for (size_t p = 0; p < per.size(); p++) per[p] = pr.periodic[p][r & (pr.periodic[p].size() - 1)];
+      airp::evaluate(pr, cur.data(), nxt.data(), per.data(), out.data());
+      for (uint32_t i = 0; i < pr.num_t; i++)
+        if (!is_zero(out[i])) {
+          *bad_row = r;
+          *bad_constraint = i;
+          return ZKP_OK;
+        }
+    }
+    for (size_t k = 0; k < pr.a_col.size(); k++) {
+      const zkp_felt e = trace_cols[(size_t)pr.a_col[k] * n + pr.a_step[k]];
+      if (!eq(make(e.lo, e.hi), pr.a_val[k])) {
+        *bad_row = pr.a_step[k];
+        *bad_assertion = (uint32_t)k;
+        return ZKP_OK;
+      }
+    }
+    return ZKP_OK;
+  } catch (const std::bad_alloc&) {
+    return ZKP_ERR_OOM;
+  } catch (...) {
+    return ZKP_ERR_ARGUMENT;
   }
 }

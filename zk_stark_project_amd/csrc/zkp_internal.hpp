@@ -277,6 +277,32 @@ void launch_lin_lincomb(Prof& prof, hipStream_t s, bool trans, bool two, const f
 void launch_eval_linear_pts(Prof& prof, hipStream_t s, const EvalCommon& c, const LinearEvalArgs& a, const felt* ev,
                             felt* comp);
 
+// A registered constraint program (include/zkp.h zkp_air_program; k_eval_program):
+// the op stream runs once per CE point, T = sum_i cc[i] * t_i over Z_T, then per group
+// of assertions that share a step sum_k cc[num_t + k] * (cur[col_k] - val_k) over (x - w^step).
+constexpr uint32_t PROG_MAX_GROUPS = 4;  // ZKP_AIR_MAX_ASSERTION_STEPS
+struct ProgPeriodic {
+  uint32_t off, mask;    // column's table at per_tab + off, indexed by (CE index & mask), mask = cycle*ce - 1
+};
+struct ProgEvalArgs {
+  const uint64_t* ops;   // device: the op stream (read through uniform loads)
+  uint32_t nops, nreg, num_t, ngroups;
+  const felt* consts;    // device: the constant pool
+  const ProgPeriodic* per_desc;  // device: one per periodic column
+  const felt* per_tab;   // device: the periodic columns over the CE domain
+  const uint32_t* a_col; // device: assertion columns, sorted by (step, column)
+  const felt* cc;        // device: num_t transition then the assertion coefficients
+  const felt* a_val;     // device: assertion values
+  uint64_t col_stride;   // felts between two columns of the trace LDE (Bl * n)
+  uint32_t grp_end[PROG_MAX_GROUPS];   // assertions [grp_end[g-1], grp_end[g]) share a step
+  felt w_step[PROG_MAX_GROUPS];        // w_n^step of the group
+  felt* dinv[PROG_MAX_GROUPS];         // M felts each: 1/(x - w^step) per CE point (cached in the ctx)
+  bool dinv_ready[PROG_MAX_GROUPS];
+  felt* binv;            // scratch: one felt per 2048 CE points
+};
+void launch_eval_program(Prof& prof, hipStream_t s, const EvalCommon& c, const ProgEvalArgs& a, const felt* lde,
+                         felt* comp);
+
 // GlobalUpdate column pairing (kernels.hip): columns d+i from columns i < d for a
 // trace whose transitions hold. check: rows [t0, t0 + 2^logtn) of pairs c0..c0+cw of
 // the natural trace (*bad = 1 on a mismatch; row 0 gives c_i); coef: the derived
