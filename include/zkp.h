@@ -260,6 +260,25 @@ int zkp_prove_device(zkp_ctx* ctx, zkp_air_id air, const void* d_trace_cols, uin
                      const zkp_proof_options* opts, uint8_t** proof, uint64_t* proof_len,
                      zkp_transcript* transcript /* nullable */);
 
+/* zkp_air_check_trace (above) for a trace in device memory (width x n zkp_felt, column-major,
+ * as zkp_prove_device takes it), checked on the device: one thread per frame (rows r, r + 1),
+ * then the assertions (k_check_program). *bad_row / *bad_constraint / *bad_assertion
+ * mean exactly what zkp_air_check_trace's mean and hold the same values for the same
+ * trace: the UINT64_MAX / UINT32_MAX sentinels, the first failing row and its first
+ * failing constraint, otherwise the first failing assertion in stored order.
+ * Status: a null pointer (ctx included) returns ZKP_ERR_ARGUMENT; otherwise the status
+ * zkp_air_check_trace returns for the same (air_id, width, n): ZKP_ERR_UNSUPPORTED_AIR
+ * for built-in and unregistered ids, ZKP_ERR_TRACE_SHAPE for a bad n or width,
+ * ZKP_ERR_PUB_INPUTS for the n-dependent refusals listed above; all of them decided on
+ * the host before any launch, so the context stays usable. n above 2^23 (the longest
+ * trace the prover takes) returns ZKP_ERR_TRACE_SHAPE. A HIP failure returns
+ * ZKP_ERR_DEVICE. Field elements that are not canonical are outside the contract, as
+ * for the host check. The call synchronises the context's stream once, to read the 16
+ * result bytes; the trace is only read. The prover never calls it: a caller that wants
+ * winterfell's debug-build validation back calls it before zkp_prove_device. */
+int zkp_air_check_trace_device(zkp_ctx* ctx, int air_id, const void* d_trace_cols, uint32_t width, uint64_t n,
+                               uint64_t* bad_row, uint32_t* bad_constraint, uint32_t* bad_assertion);
+
 /* ---- multi-GPU: coset-sharded proving ----
  * One proof is split over `world` ranks by LDE coset (rank r owns the cosets
  * [r*B/world, (r+1)*B/world)); the exchange steps are leaf-digest all-to-alls

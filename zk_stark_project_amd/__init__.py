@@ -6,11 +6,12 @@ from .air import (MimcAir, MimcInputs, GlobalUpdateAir, GlobalUpdateInputs, Trai
                   TrainingUpdateInputs, AIR_MIMC, AIR_GLOBAL_UPDATE, AIR_TRAINING_UPDATE, AirProgram,
                   RegisteredAir)
 from .prover import TraceTable, Proof, Prover, MimcProver, GlobalUpdateProver, TrainingUpdateProver, verify
-from ._native import VerifierError
+from ._native import InvalidTrace, VerifierError
 from . import helper
 
 __all__ = ["P", "GENERATOR", "TWO_ADICITY", "ProofOptions", "FieldExtension", "BatchingMethod",
            "MimcAir", "MimcInputs", "GlobalUpdateAir", "GlobalUpdateInputs", "AIR_MIMC",
            "AIR_GLOBAL_UPDATE", "AIR_TRAINING_UPDATE", "TraceTable", "Proof", "Prover",
            "MimcProver", "GlobalUpdateProver", "TrainingUpdateAir", "TrainingUpdateInputs",
-           "TrainingUpdateProver", "helper", "verify", "VerifierError", "AirProgram", "RegisteredAir"]
+           "TrainingUpdateProver", "helper", "verify", "VerifierError", "AirProgram", "RegisteredAir",
+           "InvalidTrace"]

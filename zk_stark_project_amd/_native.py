@@ -33,6 +33,17 @@ class ZkpError(RuntimeError):
         self.code = code
 
 
+class InvalidTrace(ValueError):
+    """A trace that fails its constraint program (Context.prove / prove_device with
+    validate=True): the first failing row and its first failing constraint, or, when every
+    transition holds, the step and index of the first failing assertion in stored order."""
+
+    def __init__(self, row, constraint, assertion):
+        what = f"constraint {constraint}" if constraint is not None else f"assertion {assertion}"
+        super().__init__(f"the trace fails {what} at row {row}")
+        self.row, self.constraint, self.assertion = row, constraint, assertion
+
+
 class Felt(ctypes.Structure):
     _fields_ = [("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64)]
 
@@ -82,6 +93,7 @@ EXPORTED = [
     "zkp_channel_create", "zkp_channel_destroy", "zkp_channel_commit", "zkp_channel_commit_felts",
     "zkp_channel_draw", "zkp_channel_seed", "zkp_channel_query_positions", "zkp_ctx_trim",
     "zkp_air_register", "zkp_air_unregister", "zkp_air_last_error", "zkp_air_check_trace",
+    "zkp_air_check_trace_device",
 ]
 
 # zkp_host_transport callbacks (include/zkp.h)
@@ -228,6 +240,8 @@ def load():
         L.zkp_air_last_error.restype = ctypes.c_char_p
         L.zkp_air_check_trace.argtypes = [i32, vp, u32, u64, ctypes.POINTER(u64), ctypes.POINTER(u32),
                                           ctypes.POINTER(u32)]
+        L.zkp_air_check_trace_device.argtypes = [vp, i32, vp, u32, u64, ctypes.POINTER(u64), ctypes.POINTER(u32),
+                                                 ctypes.POINTER(u32)]
         _lib = L
         return L
 
@@ -422,10 +436,40 @@ class Context:
             msg = self.lib.zkp_last_error(self.ptr) or b""
             raise ZkpError(rc, f"{what}: {msg.decode(errors='replace')}")
 
-    def prove(self, air_id: int, trace: np.ndarray, pub, options: ProofOptions, device_ptr=None):
-        """trace: (width, n, 2) uint64 host array (ignored when device_ptr is given)."""
+    def check_trace_device(self, air, d_trace: int, width: int, n: int):
+        """zkp_air_check_trace_device on a (width, n) column-major trace in device memory:
+        None for a valid trace, else (row, constraint, assertion) as air_check_trace gives it.
+        Registered ids only; synchronises the context's stream."""
+        row, con, asr = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()
+        rc = self.lib.zkp_air_check_trace_device(self.ptr, _air(air), d_trace, int(width), int(n),
+                                                 ctypes.byref(row), ctypes.byref(con), ctypes.byref(asr))
+        self._check(rc, "zkp_air_check_trace_device")
+        if row.value == 2**64 - 1:
+            return None
+        none = 2**32 - 1
+        return (row.value, None if con.value == none else con.value, None if asr.value == none else asr.value)
+
+    def check_trace(self, air, trace: np.ndarray):
+        """check_trace_device on a host (width, n, 2) uint64 array: alloc, upload, check, free."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        d = self.alloc(trace.nbytes)
+        try:
+            self.to_device(d, trace)
+            return self.check_trace_device(air, d, int(trace.shape[0]), int(trace.shape[1]))
+        finally:
+            self.free(d)
+
+    def prove(self, air_id: int, trace: np.ndarray, pub, options: ProofOptions, device_ptr=None, validate=False):
+        """trace: (width, n, 2) uint64 host array (ignored when device_ptr is given).
+        validate=True (registered ids; a built-in id raises ZkpError UNSUPPORTED_AIR) checks the
+        trace on the device first and raises InvalidTrace before any proving work."""
         w, n = int(trace.shape[0]), int(trace.shape[1])
         air_id = _air(air_id)
+        if validate:
+            bad = (self.check_trace(air_id, trace) if device_ptr is None
+                   else self.check_trace_device(air_id, device_ptr, w, n))
+            if bad is not None:
+                raise InvalidTrace(*bad)
         pubb = b"".join(int(v).to_bytes(16, "little") for v in pub)
         out = ctypes.POINTER(ctypes.c_uint8)()
         olen = ctypes.c_uint64()
@@ -483,9 +527,9 @@ class Context:
                     "zkp_comm_rccl_create")
         return Comm(p.value)
 
-    def prove_device(self, air_id, d_trace, width, n, pub, options):
+    def prove_device(self, air_id, d_trace, width, n, pub, options, validate=False):
         shape = np.empty((width, n, 0))
-        return self.prove(air_id, shape, pub, options, device_ptr=d_trace)
+        return self.prove(air_id, shape, pub, options, device_ptr=d_trace, validate=validate)
 
     # -- device memory ------------------------------------------------------
     def alloc(self, nbytes: int) -> int:

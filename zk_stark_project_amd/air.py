@@ -270,6 +270,10 @@ class RegisteredAir:
         from . import _native
         return _native.air_check_trace(self.AIR_ID, trace)
 
+    def check_trace_device(self, ctx, d_trace, n):
+        """Context.check_trace_device for this id: the trace (WIDTH x n) is in device memory."""
+        return ctx.check_trace_device(self.AIR_ID, d_trace, self.WIDTH, n)
+
     def close(self):
         if self.AIR_ID is not None:
             from . import _native

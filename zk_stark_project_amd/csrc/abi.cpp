@@ -380,6 +380,89 @@ int zkp_air_unregister(int air_id) {
 
 const char* zkp_air_last_error(void) { return airp::last_error().c_str(); }
 
+// zkp_air_check_trace on a trace in device memory (k_check_program). Every status is
+// decided on the host, in zkp_air_check_trace's order, before the first HIP call.
+int zkp_air_check_trace_device(zkp_ctx* ctx, int air_id, const void* d_trace_cols, uint32_t width, uint64_t n,
+                               uint64_t* bad_row, uint32_t* bad_constraint, uint32_t* bad_assertion) {
+  if (!ctx || !d_trace_cols || !bad_row || !bad_constraint || !bad_assertion) return ZKP_ERR_ARGUMENT;
+  return guarded(ctx, [&] {
+    if (air_id == ZKP_AIR_MIMC || air_id == ZKP_AIR_GLOBAL_UPDATE || air_id == ZKP_AIR_TRAINING_UPDATE)
+      return (int)ZKP_ERR_UNSUPPORTED_AIR;
+    if (n < 8 || (n & (n - 1)) || width == 0 || width > 255) return (int)ZKP_ERR_TRACE_SHAPE;
+    AirDesc air;
+    const int rc = build_air(air, air_id, width, n, {});
+    if (rc) return rc;
+    if (n > (1ull << MAX_LOG_TRACE)) return (int)ZKP_ERR_TRACE_SHAPE;  // the result key holds 23 bits of row
+    const airp::Program& pr = *air.prog;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    // the check's device image, in 16-byte units: [ops | constants | periodic descriptors |
+    // raw periodic values | assertion columns | assertion steps | assertion values]. It
+    // depends on the program alone; a context keeps the last id's (ids are never reused).
+    const size_t P = pr.periodic.size(), A = pr.a_col.size();
+    const size_t o_ops = 0, o_const = o_ops + (pr.ops.size() + 1) / 2, o_desc = o_const + pr.consts.size(),
+                 o_tab = o_desc + (P + 1) / 2;
+    size_t o_col = o_tab;
+    for (const auto& col : pr.periodic) o_col += col.size();
+    const size_t o_step = o_col + (A + 3) / 4, o_val = o_step + (A + 3) / 4, total = o_val + A;
+    felt* dimg = ctx->buf<felt>("check_image", total);
+    std::vector<felt>& tag = ctx->host_cache["check_image_tag"];
+    const felt want = make((uint64_t)air_id, total);
+    if (tag.size() != 1 || !eq(tag[0], want)) {
+      tag.clear();
+      std::vector<felt> img(total, zero());
+      memcpy(img.data() + o_ops, pr.ops.data(), pr.ops.size() * 8);
+      if (!pr.consts.empty()) memcpy(img.data() + o_const, pr.consts.data(), pr.consts.size() * 16);
+      ProgPeriodic* desc = reinterpret_cast<ProgPeriodic*>(img.data() + o_desc);
+      size_t off = 0;
+      for (size_t p = 0; p < P; p++) {
+        const size_t cyc = pr.periodic[p].size();
+        memcpy(img.data() + o_tab + off, pr.periodic[p].data(), cyc * 16);
+        desc[p] = ProgPeriodic{(uint32_t)off, (uint32_t)(cyc - 1)};
+        off += cyc;
+      }
+      uint32_t* steps = reinterpret_cast<uint32_t*>(img.data() + o_step);
+      for (size_t k = 0; k < A; k++) steps[k] = (uint32_t)pr.a_step[k];  // < n <= 2^23 (build_air)
+      if (A) {
+        memcpy(img.data() + o_col, pr.a_col.data(), A * 4);
+        memcpy(img.data() + o_val, pr.a_val.data(), A * 16);
+      }
+      ctx->upload(dimg, img.data(), total * 16);  // at most 224 KiB: staged in the pinned ring
+      tag.assign(1, want);
+    }
+    ProgCheckArgs ca{};
+    ca.ops = reinterpret_cast<const uint64_t*>(dimg + o_ops);
+    ca.nops = (uint32_t)pr.ops.size();
+    ca.nreg = pr.nreg;
+    ca.nassert = (uint32_t)A;
+    ca.consts = dimg + o_const;
+    ca.per_desc = reinterpret_cast<const ProgPeriodic*>(dimg + o_desc);
+    ca.per_tab = dimg + o_tab;
+    ca.a_col = reinterpret_cast<const uint32_t*>(dimg + o_col);
+    ca.a_step = reinterpret_cast<const uint32_t*>(dimg + o_step);
+    ca.a_val = dimg + o_val;
+    ca.n = n;
+    unsigned long long* dres = ctx->buf<unsigned long long>("check_result", 2);
+    HIP_CHECK(hipMemsetAsync(dres, 0xff, 16, ctx->stream));
+    launch_check_program(ctx->prof, ctx->stream, ca, width, (const felt*)d_trace_cols, dres);
+    unsigned long long res[2];
+    ctx->download(res, dres, 16);  // the call's one stream synchronise
+    ctx->collect_prof();
+    ctx->free_retired();
+    // the host check's precedence: a failing transition wins over any assertion
+    *bad_row = UINT64_MAX;
+    *bad_constraint = UINT32_MAX;
+    *bad_assertion = UINT32_MAX;
+    if (res[0] != ~0ull) {
+      *bad_row = res[0] >> 10;
+      *bad_constraint = (uint32_t)(res[0] & 1023);
+    } else if (res[1] != ~0ull) {
+      *bad_row = pr.a_step[res[1]];
+      *bad_assertion = (uint32_t)res[1];
+    }
+    return 0;
+  });
+}
+
 // Host-side MiMC AIR trace builder (trace construction, like TraceTable building
 // in the reference; not part of the proving hot path).
 int zkp_build_mimc_trace(const uint8_t seed[16], uint64_t n, zkp_felt* out) {

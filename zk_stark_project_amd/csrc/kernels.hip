@@ -463,6 +463,76 @@ __global__ __launch_bounds__(PROG_TPB) void k_eval_program(EvalCommon c, ProgEva
   comp[q] = v;
 }
 
+// A natural (column-major, not extended) trace against a registered constraint
+// program: what zkp_air_check_trace does on the host. Blocks [0, frame_blocks) take one
+// frame (rows r, r + 1) per thread, r in [0, n - 2]: row n - 1 starts no frame and nothing
+// wraps to row 0, so a lane with r >= n - 1 returns before its first load. The
+// interpreter is k_eval_program's (uniform op / constant fetches, registers in LDS as
+// [register][thread], one wave per block, canonical field ops) with three differences:
+// CUR / NEXT read T[c*n + r] / T[c*n + r + 1], PERIODIC reads the column's raw value
+// per_tab[off + (r & (cycle - 1))], and an EMIT tests its operand against zero. A lane
+// keeps the index of its first non-zero EMIT and still runs the stream to its end (the
+// stream is wave-uniform). Keys (r << 10) | constraint grow with the lane, so the
+// wave's minimum is the key of its lowest failing lane (one ballot); that lane alone
+// does a 64-bit atomicMin on res[0]. A valid trace issues no atomic.
+// The blocks after them check the assertions, thread k the stored assertion k, with the
+// same ballot and an atomicMin of k on res[1].
+__global__ __launch_bounds__(PROG_TPB) void k_check_program(ProgCheckArgs a, const felt* __restrict__ T,
+                                                            unsigned long long* __restrict__ res) {
+  extern __shared__ __align__(16) unsigned char check_lds[];
+  if (blockIdx.x >= a.frame_blocks) {
+    const uint32_t k = (blockIdx.x - a.frame_blocks) * PROG_TPB + threadIdx.x;
+    if (k >= a.nassert) return;
+    const bool fail = !eq(T[(uint64_t)a.a_col[k] * a.n + a.a_step[k]], a.a_val[k]);
+    const uint64_t failing = __builtin_amdgcn_ballot_w64(fail);
+    if (failing && threadIdx.x == (uint32_t)__builtin_ctzll(failing)) atomicMin(res + 1, (unsigned long long)k);
+    return;
+  }
+  lds_u32x4* const rg = (lds_u32x4*)check_lds + threadIdx.x;
+  const uint64_t r = (uint64_t)blockIdx.x * PROG_TPB + threadIdx.x;
+  if (r + 1 >= a.n) return;
+  const felt* const cur = T + r;
+  auto fetch = [&](uint32_t operand) -> felt {
+    const uint32_t idx = operand & 0x1fff;
+    switch (operand >> 13) {
+      case ZKP_SRC_REG: {
+        const u32x4 v = rg[idx * PROG_TPB];
+        return make((uint64_t)v.x | ((uint64_t)v.y << 32), (uint64_t)v.z | ((uint64_t)v.w << 32));
+      }
+      case ZKP_SRC_CUR: return cur[idx * a.n];
+      case ZKP_SRC_NEXT: return cur[idx * a.n + 1];
+      case ZKP_SRC_PERIODIC: {
+        const ProgPeriodic d = a.per_desc[idx];
+        return a.per_tab[d.off + ((uint32_t)r & d.mask)];
+      }
+      default: return a.consts[idx];
+    }
+  };
+  constexpr uint32_t NONE = 0xffffffffu;
+  uint32_t bad = NONE, emitted = 0;
+  for (uint32_t pc = 0; pc < a.nops; pc++) {
+    const uint64_t op = a.ops[pc];
+    const uint32_t code = (uint32_t)op & 0xff;
+    const felt x = fetch((uint32_t)(op >> 16) & 0xffff);
+    if (code == ZKP_OP_EMIT) {
+      if (bad == NONE && !is_zero(x)) bad = emitted;
+      emitted++;
+      continue;
+    }
+    const felt y = fetch((uint32_t)(op >> 32) & 0xffff);
+    felt v;
+    if (code == ZKP_OP_ADD) v = add(x, y);
+    else if (code == ZKP_OP_SUB) v = sub(x, y);
+    else v = mul(x, y);
+    u32x4 w;
+    w.x = (uint32_t)v.lo; w.y = (uint32_t)(v.lo >> 32); w.z = (uint32_t)v.hi; w.w = (uint32_t)(v.hi >> 32);
+    rg[((uint32_t)(op >> 8) & 0xff) * PROG_TPB] = w;
+  }
+  const uint64_t failing = __builtin_amdgcn_ballot_w64(bad != NONE);
+  if (failing && threadIdx.x == (uint32_t)__builtin_ctzll(failing))
+    atomicMin(res, (unsigned long long)((r << 10) | bad));
+}
+
 // Linear AIRs. TRANS: transition sum_c a_c*next_c + b_c*cur_c divided by Z_T
 // (GlobalUpdate); without it the transition part is identically zero
 // (TrainingUpdate). Boundary: group 0 = sum_c beta0_c*cur_c - bconst0
@@ -1375,6 +1445,18 @@ void launch_eval_program(Prof& prof, hipStream_t s, const EvalCommon& c, const P
   const size_t lds = (size_t)a.nreg * PROG_TPB * sizeof(felt);
   LAUNCH(prof, "eval_program", s, (double)M * 48.0,
          hipLaunchKernelGGL(k_eval_program, dim3(blocks_for(M, PROG_TPB)), dim3(PROG_TPB), lds, s, c, a, lde, comp));
+}
+
+void launch_check_program(Prof& prof, hipStream_t s, ProgCheckArgs a, uint32_t width, const felt* T,
+                          unsigned long long* res) {
+  if (a.nreg == 0 || a.nreg > ZKP_AIR_MAX_REGISTERS || a.nassert > ZKP_AIR_MAX_ASSERTIONS || a.n < 2 ||
+      a.n > (1ull << MAX_LOG_TRACE))
+    launch_fail(ZKP_ERR_ARGUMENT, "trace check outside the kernel's limits");
+  a.frame_blocks = blocks_for(a.n - 1, PROG_TPB);
+  const uint32_t blocks = a.frame_blocks + blocks_for(a.nassert, PROG_TPB);
+  const size_t lds = (size_t)a.nreg * PROG_TPB * sizeof(felt);
+  LAUNCH(prof, "check_program", s, (double)width * (double)a.n * 16.0,
+         hipLaunchKernelGGL(k_check_program, dim3(blocks), dim3(PROG_TPB), lds, s, a, T, res));
 }
 
 void launch_eval_linear(Prof& prof, hipStream_t s, const EvalCommon& c, const LinearEvalArgs& a, const felt* lde,

@@ -303,6 +303,24 @@ struct ProgEvalArgs {
 void launch_eval_program(Prof& prof, hipStream_t s, const EvalCommon& c, const ProgEvalArgs& a, const felt* lde,
                          felt* comp);
 
+// The natural trace T (column-major, width x n) against a registered program
+// (k_check_program; zkp_air_check_trace_device): one frame per thread, then the
+// assertions. res[0] (preset to UINT64_MAX) receives the minimum (row << 10) | constraint
+// over the failing frames, res[1] the minimum index of a failing assertion.
+struct ProgCheckArgs {
+  const uint64_t* ops;   // device: the op stream
+  uint32_t nops, nreg, nassert, frame_blocks;  // frame_blocks: set by the launcher
+  const felt* consts;    // device: the constant pool
+  const ProgPeriodic* per_desc;  // device: one per periodic column, mask = cycle - 1
+  const felt* per_tab;   // device: the periodic columns' raw values, indexed by (row & mask)
+  const uint32_t* a_col; // device: assertion columns, steps and values in stored (step, column) order
+  const uint32_t* a_step;
+  const felt* a_val;
+  uint64_t n;            // 2 <= n <= 2^MAX_LOG_TRACE
+};
+void launch_check_program(Prof& prof, hipStream_t s, ProgCheckArgs a, uint32_t width, const felt* T,
+                          unsigned long long* res);
+
 // GlobalUpdate column pairing (kernels.hip): columns d+i from columns i < d for a
 // trace whose transitions hold. check: rows [t0, t0 + 2^logtn) of pairs c0..c0+cw of
 // the natural trace (*bad = 1 on a mismatch; row 0 gives c_i); coef: the derived
