@@ -137,10 +137,50 @@ int zkp_air_register(const zkp_air_program* program, int* air_id);
  * already running under it keep their copy. */
 int zkp_air_unregister(int air_id);
 const char* zkp_air_last_error(void);
+
+/* Strided assertions (winterfell `Assertion::periodic` and `Assertion::sequence`),
+ * registered beside a program's single-row ones. With k = n / stride:
+ *   periodic (num_values = 0): T[column][first_step + stride*i] = value for every i < k;
+ *   sequence (num_values = k): T[column][first_step + stride*i] = values[i].
+ * stride is a power of two >= 2 and first_step < stride. All assertions of an AIR are
+ * kept sorted by (stride, first_step, column), stride counting as 0 for the single-row
+ * ones: the singles come first in their (step, column) order, the strided ones follow,
+ * and each takes one composition coefficient in that order (the proof's context counts
+ * each once). Assertions that share (stride, first_step) form one group with the divisor
+ * x^k - w_n^(first_step * k); a group's term is sum_j cc_j * (T_col_j(x) - V_j(x)) over it,
+ * V_j the constant `value`, or for a sequence P_j(x * w_n^-first_step) with P_j the
+ * polynomial of degree < k through values[i] at w_k^i (w_k = w_n^stride). A sequence of
+ * equal values therefore gives the field elements of the periodic form, and stride = n
+ * those of a single-row assertion at first_step.
+ * Registration refuses (ZKP_ERR_ARGUMENT, zkp_air_last_error() names strided[i]): a
+ * stride that is not a power of two >= 2, first_step >= stride, a column outside the
+ * width, a value that is not canonical, a num_values that is not a power of two, a
+ * sequence without values, more than ZKP_AIR_MAX_SEQUENCE_VALUES sequence values in the
+ * program, more than ZKP_AIR_MAX_ASSERTIONS assertions (single and strided together),
+ * more than ZKP_AIR_MAX_STRIDED_GROUPS distinct (stride, first_step), and two assertions
+ * over one cell: on one column, strided against strided when first_a = first_b modulo
+ * the smaller stride, single against strided when step = first_step modulo stride.
+ * num_strided = 0 is zkp_air_register. The singles keep their limit of 4 steps. */
+enum {
+  ZKP_AIR_MAX_STRIDED_GROUPS = 4,
+  ZKP_AIR_MAX_SEQUENCE_VALUES = 1 << 18 /* per program, all sequences together */
+};
+typedef struct zkp_air_strided_assertion {
+  uint32_t column;
+  uint32_t num_values;     /* 0: periodic, `value` holds; >= 1 (a power of two): sequence of that many `values` */
+  uint64_t first_step;
+  uint64_t stride;
+  zkp_felt value;
+  const zkp_felt* values;  /* null for periodic */
+} zkp_air_strided_assertion;
+int zkp_air_register_strided(const zkp_air_program* program, const zkp_air_strided_assertion* strided,
+                             uint32_t num_strided, int* air_id);
+
 /* Checks that need the trace length n. A registered id's entry points return
  * ZKP_ERR_PUB_INPUTS (zkp_verify: ZKP_VERIFY_PUB_INPUTS) for:
  *  - a width other than the program's;
  *  - an assertion step >= n;
+ *  - a strided assertion's stride > n, or a sequence with num_values * stride != n;
  *  - a periodic cycle > n;
  *  - an n that divides d - 1, d being the largest declared degree (degree 9 over
  *    8 rows). The quotient of a degree-d constraint has (d-1)(n-1) + 1 coefficients.
@@ -153,7 +193,13 @@ const char* zkp_air_last_error(void);
  * Memory: a context keeps the device image of one program (the last id, n and
  * blowup it evaluated), and one table of n * ce divisor inverses per distinct
  * (domain, assertion step) it has met, like the built-in ids' tables. Instances
- * that assert other rows therefore add tables until the context is destroyed. */
+ * that assert other rows therefore add tables until the context is destroyed.
+ * A strided group adds, per distinct (n, ce, stride, first_step), one table of
+ * stride * ce divisor inverses (x^k depends on the CE index modulo stride * ce only),
+ * kept like the single-step tables. The image also carries each sequence's k
+ * interpolated coefficients. A group that holds a sequence costs, per proof, one
+ * column of n coefficients and its n * ce evaluations; those two buffers are shared
+ * by all instances and sized by the largest shape met. */
 
 /* Host-only trace validation (winterfell's debug-build `validate` of a trace,
  * which `Prover::prove` runs before proving): every transition constraint on the
@@ -162,7 +208,9 @@ const char* zkp_air_last_error(void);
  * either the first failing row and its first failing constraint in *bad_row /
  * *bad_constraint (*bad_assertion = UINT32_MAX), or, when every transition holds,
  * *bad_row = the step of the first failing assertion (in stored order) and its
- * index in *bad_assertion (*bad_constraint = UINT32_MAX). Registered ids only:
+ * index in *bad_assertion (*bad_constraint = UINT32_MAX). The stored order is the
+ * singles, then the strided assertions; a strided assertion reports its lowest
+ * failing row. Registered ids only:
  * the built-in ids return ZKP_ERR_UNSUPPORTED_AIR. */
 int zkp_air_check_trace(int air_id, const zkp_felt* trace_cols, uint32_t width, uint64_t n, uint64_t* bad_row,
                         uint32_t* bad_constraint, uint32_t* bad_assertion);

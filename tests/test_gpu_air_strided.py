@@ -1,0 +1,252 @@
+"""Strided assertions (`Assertion::periodic`, `Assertion::sequence`) on the GPU:
+k_eval_program_strided, k_strided_combine, the strided divisor tables and the asserted
+cells of k_check_program (csrc/kernels.hip).
+
+1. Byte anchor: MiMC with its result asserted over the stride n, as a sequence and as a
+   periodic assertion, gives the built-in id's proof byte for byte (the built-in id is
+   pinned by the CPU oracle elsewhere).
+2. Session.eval_constraints equals the composition formula at every CE point, exactly.
+3. End to end at n = 8, 16 and 4096: checked, proved, verified, mutated.
+4. The device trace check equals the host's for failures placed across the assertion blocks.
+5. The stage route and a one-rank communicator; 6. two ids in turn on one context.
+Integer arithmetic throughout: no tolerance."""
+import functools
+
+import numpy as np
+import pytest
+
+from air_program_cases import trace_array
+from air_strided_cases import composition_spec, mimc_strided_program, strided_program, strided_trace
+from option_cases import ALGEBRAIC
+from proof_format import sections
+from test_gpu_options import mimc_inputs
+from zk_stark_project_amd import AIR_MIMC, InvalidTrace, ProofOptions, _native
+from zk_stark_project_amd._native import verify_status
+from zk_stark_project_amd.field import P, unpack
+
+pytestmark = pytest.mark.gpu
+
+
+def opts_of(q, blowup, grind, fold=16, r=7):
+    return ProofOptions(q, blowup, grind, 1, fold, r, ALGEBRAIC, ALGEBRAIC)
+
+
+@functools.lru_cache(maxsize=None)
+def cols_of(d, n):
+    return strided_trace(d, n)
+
+
+def changed(cols, *cells):
+    out = [list(c) for c in cols]
+    for col, row in cells:
+        out[col][row] = (out[col][row] + 1) % P
+    return out
+
+
+# ---------------------------------------------------------------- 1. byte anchor
+@functools.lru_cache(maxsize=None)
+def builtin_mimc_proof(ctx, n, blowup, fold):
+    _, trace, pub = mimc_inputs(n)
+    proof, tr = ctx.prove(AIR_MIMC, trace.data, pub, opts_of(20, blowup, 4, fold))
+    return proof, tr.summary()
+
+
+@pytest.mark.parametrize("form", ["sequence", "periodic"])
+@pytest.mark.parametrize("fold", [2, 16])
+@pytest.mark.parametrize("blowup", [8, 16])
+@pytest.mark.parametrize("n", [64, 1024])
+def test_mimc_result_strided_equals_builtin(ctx, n, blowup, fold, form):
+    """stride = n: the largest table (stride * ce = the CE domain), W extended from a constant,
+    every coefficient index. blowup 8: ce = B, the derived last column; 16: ce < B."""
+    _, trace, pub = mimc_inputs(n)
+    opts = opts_of(20, blowup, 4, fold)
+    ref, summary = builtin_mimc_proof(ctx, n, blowup, fold)
+    with mimc_strided_program(n, pub, form).register() as prog:
+        got, tr = ctx.prove(prog, trace.data, pub, opts)
+        assert tr.summary() == summary
+        assert got == ref
+        assert verify_status(prog, got, pub, opts) == 0
+    assert verify_status(AIR_MIMC, got, pub, opts) == 0
+
+
+# ---------------------------------------------------------------- 2. every CE point against the formula
+@pytest.mark.parametrize("d,n,blowup,full", [(3, 16, 4, False), (5, 8, 4, False), (3, 16, 4, True), (5, 8, 4, True)])
+def test_constraint_evaluations_equal_the_formula(ctx, d, n, blowup, full):
+    """(3, 16, 4): ce = 2 below the blowup; (5, 8, 4): ce = 4 = B. Two singles, the group
+    (stride 4, first 1) with a periodic and a sequence entry, the group (stride 2, first 0) with
+    a sequence; `full` adds a group of stride n. The coefficients come from the channel."""
+    cols = cols_of(d, n)
+    p = strided_program(d, n, full=full)
+    pub = [cols[0][0], cols[1][0]]
+    opts = opts_of(20, blowup, 4)
+    with p.register() as prog:
+        assert prog.num_coeffs == 3 + 2 + (4 if full else 3)
+        ch = _native.Channel(prog, 3, n, pub, opts)
+        s = _native.Session(ctx, prog, 3, n, pub, opts)
+        try:
+            ch.commit(s.trace_lde(trace_array(cols)))
+            coeffs = ch.draw_coeffs(opts.batching_constraints, prog.num_coeffs)
+            evals = unpack(s.eval_constraints(coeffs))
+        finally:
+            s.close()
+            ch.close()
+    assert s.ce == {3: 2, 5: 4}[d] and len(evals) == n * s.ce
+    assert evals == composition_spec(p, cols, s.ce, coeffs)
+
+
+# ---------------------------------------------------------------- 3. end to end
+def section_offsets(proof):
+    """Byte offset of the middle of every section of the wire format (proof_format.sections)."""
+    sec = sections(proof)
+    at, o = {}, 0
+    at["context"] = 3                     # log2 of the trace length
+    o = len(sec["context"]) + 1           # + the unique-query count
+    at["commitments"] = o + 2 + len(sec["commitments"]) // 2
+    o += 2 + len(sec["commitments"])
+    at["queries"] = o + len(sec["queries"]) // 2
+    o += len(sec["queries"])
+    at["ood_trace"] = o + 3 + len(sec["ood_trace"]) // 2
+    o += 3 + len(sec["ood_trace"])
+    at["ood_comp"] = o + 2 + len(sec["ood_comp"]) // 2
+    o += 2 + len(sec["ood_comp"])
+    at["fri_queries"] = o + len(sec["fri_queries"]) // 2
+    o += len(sec["fri_queries"])
+    at["remainder"] = o + 2 + len(sec["remainder"]) // 2
+    o += 2 + len(sec["remainder"]) + 1
+    at["nonce"] = o
+    assert o + 9 == len(proof)
+    return at
+
+
+@pytest.mark.parametrize("d,n,blowup", [(5, 8, 4), (3, 16, 4), (5, 4096, 8)])
+def test_proves_and_verifies(ctx, d, n, blowup):
+    """n = 4096 has FRI layers and 64 blocks per CE coset; its groups' tables have 16 and 8
+    entries per CE coset and W two columns of n coefficients."""
+    cols = cols_of(d, n)
+    data = trace_array(cols)
+    pub = [cols[0][0], cols[1][n - 1]]
+    opts = opts_of(20, blowup, 4)
+    with strided_program(d, n, full=True).register() as prog:
+        assert prog.check_trace(data) is None
+        assert ctx.check_trace(prog, data) is None
+        proof, _ = ctx.prove(prog, data, pub, opts, validate=True)
+        assert verify_status(prog, proof, pub, opts) == 0
+        for name, at in section_offsets(proof).items():
+            bad = bytearray(proof)
+            bad[at] ^= 0x10
+            assert verify_status(prog, bytes(bad), pub, opts) != 0, name
+    # one sequence value of the registered program changed: the middle cell of column 0's sequence
+    row = 1 + 4 * (n // 8)
+    with strided_program(d, n, cols=changed(cols, (0, row)), full=True).register() as prog:
+        assert verify_status(prog, proof, pub, opts) != 0
+        want = (row, None, 3)
+        assert prog.check_trace(data) == want
+        assert ctx.check_trace(prog, data) == want
+        with pytest.raises(InvalidTrace):
+            ctx.prove(prog, data, pub, opts, validate=True)
+        forged, _ = ctx.prove(prog, data, pub, opts)
+        assert verify_status(prog, forged, pub, opts) != 0
+    # and the periodic value
+    with strided_program(d, n, cols=changed(cols, (2, 1))).register() as prog:
+        assert ctx.check_trace(prog, data) == prog.check_trace(data) == (1, None, 4)
+        forged, _ = ctx.prove(prog, data, pub, opts)
+        assert verify_status(prog, forged, pub, opts) != 0
+
+
+def test_strided_assertions_alone(ctx):
+    """No single assertion: no single-step group or value table, the strided coefficients follow
+    the transition ones directly."""
+    d, n = 3, 8
+    cols = cols_of(d, n)
+    data = trace_array(cols)
+    opts = opts_of(20, 2, 4)
+    p = strided_program(d, n)
+    p.assertions = []
+    with p.register() as prog:
+        assert prog.num_coeffs == 6
+        assert ctx.check_trace(prog, data) is None
+        proof, _ = ctx.prove(prog, data, [7], opts)
+        assert verify_status(prog, proof, [7], opts) == 0
+        forged, _ = ctx.prove(prog, trace_array(changed(cols, (1, 4))), [7], opts)
+        assert verify_status(prog, forged, [7], opts) != 0
+
+
+# ---------------------------------------------------------------- 4. the device check equals the host's
+@pytest.mark.parametrize("n", [8, 4096])
+def test_device_check_equals_host_check(ctx, n):
+    """The frames always pass (one constant-0 constraint), so only asserted cells decide.
+    n = 8: every assertion is one partial wave (4, 2 and 2 cells). n = 4096: column 1's
+    sequence has 2048 cells in 32 blocks, the two stride-4 assertions 1024 cells in 16."""
+    d = 5
+    cols = cols_of(d, n)
+    with strided_program(d, n, transitions=False).register() as prog:
+        def both(*cells):
+            data = trace_array(changed(cols, *cells))
+            want = prog.check_trace(data)
+            assert ctx.check_trace(prog, data) == want
+            return want
+        assert both() is None
+        k2 = n // 2  # cells of column 1's sequence (stride 2, first 0): assertion 2
+        lanes = [0, k2 - 1] if n == 8 else [0, 63, 64, 127, 64 * 31, k2 - 1]
+        for i in lanes:  # the lowest and highest lane of a block, first and last block
+            assert both((1, 2 * i)) == (2 * i, None, 2)
+        k4 = n // 4  # column 0's sequence (stride 4, first 1): assertion 3; the periodic one: 4
+        for i in ([0, k4 - 1] if n == 8 else [63, 64, k4 - 1]):
+            assert both((0, 1 + 4 * i)) == (1 + 4 * i, None, 3)
+        assert both((2, n - 3)) == (n - 3, None, 4)          # the last cell of the last assertion
+        assert both((2, n - 3), (2, 1)) == (1, None, 4)      # two cells of it: the lowest row
+        assert both((2, 1), (0, n - 3), (1, n - 2)) == (n - 2, None, 2)  # three assertions: the first stored
+        assert both((0, 5), (2, 1)) == (5, None, 3)
+        assert both((1, n - 1), (1, 0)) == (n - 1, None, 1)  # a single comes before every strided one
+        assert both((1, 1), (2, 0)) is None                  # cells nobody asserts
+
+
+# ---------------------------------------------------------------- 5. the stage route, a one-rank communicator
+def test_stages_and_one_rank_group_equal_prove(ctx):
+    """n = 256, blowup 8: two FRI layers. prove_by_stages runs the session's constraint stage."""
+    d, n = 5, 256
+    cols = cols_of(d, n)
+    data = trace_array(cols)
+    pub = [cols[0][0], cols[1][0]]
+    opts = opts_of(20, 8, 4)
+    with strided_program(d, n).register() as prog:
+        gpu, tr = ctx.prove(prog, data, pub, opts)
+        assert verify_status(prog, gpu, pub, opts) == 0
+        want = tr.summary()
+        got = _native.prove_by_stages(ctx, prog, data, pub, opts, prog.num_coeffs)
+        assert got["trace_root"].hex() == want["trace_root"]
+        assert got["constraint_root"].hex() == want["constraint_root"]
+        assert got["z"] == want["z"]
+        assert [r.hex() for r in got["fri_roots"]] == want["fri_roots"] and len(want["fri_roots"]) == 2
+        assert got["remainder_commitment"].hex() == want["remainder_commitment"]
+        assert got["pow_nonce"] == want["pow_nonce"]
+        assert got["query_positions"] == want["query_positions"]
+        sec = sections(gpu)
+        assert got["queries"] == sec["queries"] + sec["fri_queries"]
+        one = _native.local_group(1)[0]
+        try:
+            assert ctx.prove_sharded(one, prog, data, pub, opts)[0] == gpu
+        finally:
+            one.close()
+
+
+# ---------------------------------------------------------------- 6. two ids in turn
+def test_two_ids_in_turn(ctx):
+    """Two programs that differ in one sequence value, proved alternately on one context: every
+    proof is made from its own program's image, tables and sequence coefficients."""
+    d, n = 3, 16
+    cols = cols_of(d, n)
+    other = changed(cols, (0, 5))
+    opts = opts_of(20, 4, 4)
+    pa, pb = strided_program(d, n, transitions=False), strided_program(d, n, cols=other, transitions=False)
+    assert [x != y for x, y in zip(pa.sorted_strided_assertions(), pb.sorted_strided_assertions())] == [
+        False, True, False]
+    with pa.register() as a, pb.register() as b:
+        first, _ = ctx.prove(a, trace_array(cols), [1], opts)
+        second, _ = ctx.prove(b, trace_array(other), [1], opts)
+        again, _ = ctx.prove(a, trace_array(cols), [1], opts)
+        assert first == again != second
+        assert verify_status(a, again, [1], opts) == 0 and verify_status(b, second, [1], opts) == 0
+        assert verify_status(b, again, [1], opts) != 0 and verify_status(a, second, [1], opts) != 0
+        assert ctx.check_trace(a, trace_array(other)) == ctx.check_trace(b, trace_array(cols)) == (5, None, 3)
+        assert ctx.check_trace(b, trace_array(other)) is None

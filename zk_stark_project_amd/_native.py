@@ -93,7 +93,7 @@ EXPORTED = [
     "zkp_channel_create", "zkp_channel_destroy", "zkp_channel_commit", "zkp_channel_commit_felts",
     "zkp_channel_draw", "zkp_channel_seed", "zkp_channel_query_positions", "zkp_ctx_trim",
     "zkp_air_register", "zkp_air_unregister", "zkp_air_last_error", "zkp_air_check_trace",
-    "zkp_air_check_trace_device",
+    "zkp_air_check_trace_device", "zkp_air_register_strided",
 ]
 
 # zkp_host_transport callbacks (include/zkp.h)
@@ -133,6 +133,12 @@ class AirAssertionC(ctypes.Structure):
     """`zkp_air_assertion` (include/zkp.h)."""
     _fields_ = [("column", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("step", ctypes.c_uint64),
                 ("value", Felt)]
+
+
+class AirStridedAssertionC(ctypes.Structure):
+    """`zkp_air_strided_assertion` (include/zkp.h)."""
+    _fields_ = [("column", ctypes.c_uint32), ("num_values", ctypes.c_uint32), ("first_step", ctypes.c_uint64),
+                ("stride", ctypes.c_uint64), ("value", Felt), ("values", ctypes.POINTER(Felt))]
 
 
 class AirProgramC(ctypes.Structure):
@@ -235,6 +241,8 @@ def load():
         L.zkp_channel_seed.argtypes = [vp, ctypes.c_char_p]
         L.zkp_channel_query_positions.argtypes = [vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u32)]
         L.zkp_air_register.argtypes = [ctypes.POINTER(AirProgramC), ctypes.POINTER(i32)]
+        L.zkp_air_register_strided.argtypes = [ctypes.POINTER(AirProgramC), ctypes.POINTER(AirStridedAssertionC), u32,
+                                               ctypes.POINTER(i32)]
         L.zkp_air_unregister.argtypes = [i32]
         L.zkp_air_last_error.argtypes = []
         L.zkp_air_last_error.restype = ctypes.c_char_p
@@ -246,10 +254,11 @@ def load():
         return L
 
 
-def air_register(width: int, degrees, constants, periodic, assertions, num_registers: int, ops) -> int:
-    """zkp_air_register: `periodic` is a list of value lists, `assertions` (column, step, value)
-    triples, `ops` encoded op words. Returns the new id; a refused program raises ZkpError
-    with the failing field in its message."""
+def air_register(width: int, degrees, constants, periodic, assertions, num_registers: int, ops, strided=()) -> int:
+    """zkp_air_register_strided: `periodic` is a list of value lists, `assertions` (column, step,
+    value) triples, `ops` encoded op words, `strided` (column, first_step, stride, value or list of
+    values) tuples: an int is `Assertion::periodic`, a list `Assertion::sequence`. Returns the
+    new id; a refused program raises ZkpError with the failing field in its message."""
     L = load()
     mask = 2**64 - 1
     felts = lambda vals: (Felt * max(1, len(vals)))(*[Felt(int(v) & mask, int(v) >> 64) for v in vals])
@@ -267,10 +276,20 @@ def air_register(width: int, degrees, constants, periodic, assertions, num_regis
     pc.num_assertions, pc.assertions = len(assertions), asr
     opw = (ctypes.c_uint64 * max(1, len(ops)))(*ops)
     pc.num_registers, pc.num_ops, pc.ops = num_registers, len(ops), opw
+    keep, rows = [], []  # the sequences' value arrays stay referenced until the call returns
+    for col, first, stride, val in strided:
+        if isinstance(val, (list, tuple)):
+            arr = felts(val)
+            keep.append(arr)
+            rows.append(AirStridedAssertionC(col, len(val), first, stride, Felt(0, 0), arr))
+        else:
+            rows.append(AirStridedAssertionC(col, 0, first, stride, Felt(int(val) & mask, int(val) >> 64), None))
+    sta = (AirStridedAssertionC * max(1, len(rows)))(*rows)
     out = ctypes.c_int()
-    rc = L.zkp_air_register(ctypes.byref(pc), ctypes.byref(out))
+    rc = L.zkp_air_register_strided(ctypes.byref(pc), sta, len(rows), ctypes.byref(out))
     if rc:
-        raise ZkpError(rc, "zkp_air_register: " + (L.zkp_air_last_error() or b"").decode(errors="replace"))
+        entry = "zkp_air_register_strided: " if rows else "zkp_air_register: "
+        raise ZkpError(rc, entry + (L.zkp_air_last_error() or b"").decode(errors="replace"))
     return out.value
 
 

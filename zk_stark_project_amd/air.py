@@ -258,7 +258,7 @@ class RegisteredAir:
         self.AIR_ID = air_id
         self.WIDTH = program.width
         self.num_constraints = len(program.constraints)
-        self.num_assertions = len(program.assertions)
+        self.num_assertions = len(program.assertions) + len(program.strided_assertions)
         self.num_coeffs = self.num_constraints + self.num_assertions  # composition coefficients
 
     def __int__(self):
@@ -316,6 +316,7 @@ class AirProgram:
         self.periodic_columns = []
         self.constraints = []  # (Expr, degree)
         self.assertions = []   # (column, step, value)
+        self.strided_assertions = []  # (column, first_step, stride, value | [values])
 
     # -- expression nodes
     def _leaf(self, kind, index):
@@ -357,9 +358,24 @@ class AirProgram:
         """`Assertion::single(column, step, value)`."""
         self.assertions.append((int(column), int(step), int(value) % P))
 
+    def periodic_assertion(self, column: int, first_step: int, stride: int, value: int):
+        """`Assertion::periodic(column, first_step, stride, value)`: the column holds `value` at
+        first_step + stride * i for every i < n / stride (stride a power of two >= 2)."""
+        self.strided_assertions.append((int(column), int(first_step), int(stride), int(value) % P))
+
+    def sequence_assertion(self, column: int, first_step: int, stride: int, values):
+        """`Assertion::sequence(column, first_step, stride, values)`: the column holds values[i] at
+        first_step + stride * i; len(values) = n / stride, a power of two."""
+        self.strided_assertions.append((int(column), int(first_step), int(stride), [int(v) % P for v in values]))
+
     def sorted_assertions(self):
-        """The assertions in the order their composition coefficients are drawn: (step, column)."""
+        """The single assertions in the order their composition coefficients are drawn: (step, column)."""
         return sorted(self.assertions, key=lambda a: (a[1], a[0]))
+
+    def sorted_strided_assertions(self):
+        """The strided assertions in the order their coefficients are drawn, after the singles':
+        (stride, first_step, column)."""
+        return sorted(self.strided_assertions, key=lambda a: (a[2], a[1], a[0]))
 
     # -- the spec
     def evaluate(self, cur_row, next_row, row_index: int = 0, periodic=None):
@@ -444,11 +460,12 @@ class AirProgram:
         return CompiledProgram(ops, max(used, 1))
 
     def register(self) -> RegisteredAir:
-        """zkp_air_register: validates the program and returns its id holder."""
+        """zkp_air_register_strided: validates the program and returns its id holder."""
         from . import _native
         cp = self.compile()
         aid = _native.air_register(self.width, [d for _, d in self.constraints], self.constants,
-                                   self.periodic_columns, self.assertions, cp.num_registers, cp.ops)
+                                   self.periodic_columns, self.assertions, cp.num_registers, cp.ops,
+                                   self.strided_assertions)
         return RegisteredAir(aid, self)
 
     def check_trace(self, trace):

@@ -351,6 +351,11 @@ int zkp_kernel_stats_table(zkp_ctx* ctx, char** table) {
 
 // ---- caller-defined AIRs: the table of constraint programs (air_program.hpp). Host-only.
 int zkp_air_register(const zkp_air_program* program, int* air_id) {
+  return zkp_air_register_strided(program, nullptr, 0, air_id);
+}
+
+int zkp_air_register_strided(const zkp_air_program* program, const zkp_air_strided_assertion* strided,
+                             uint32_t num_strided, int* air_id) {
   std::string& err = airp::last_error();
   err.clear();
   try {
@@ -360,6 +365,7 @@ int zkp_air_register(const zkp_air_program* program, int* air_id) {
     }
     auto p = std::make_shared<airp::Program>();
     err = airp::validate(program, *p);
+    if (err.empty()) err = airp::validate_strided(strided, num_strided, *p);
     if (!err.empty()) return ZKP_ERR_ARGUMENT;
     *air_id = airp::insert(std::move(p));
     return ZKP_OK;
@@ -403,10 +409,20 @@ int zkp_air_check_trace_device(zkp_ctx* ctx, int air_id, const void* d_trace_col
                  o_tab = o_desc + (P + 1) / 2;
     size_t o_col = o_tab;
     for (const auto& col : pr.periodic) o_col += col.size();
-    const size_t o_step = o_col + (A + 3) / 4, o_val = o_step + (A + 3) / 4, total = o_val + A;
+    // Strided assertions append [cell descriptors (3 units each) | sequence values]; their
+    // cell counts and block runs depend on n, so the tag carries it too.
+    static_assert(sizeof(ProgStridedCells) == 48, "three 16-byte units");
+    const std::vector<airp::Strided>& sv = pr.strided;
+    const size_t S = sv.size();
+    size_t seq_felts = 0;
+    for (const airp::Strided& a : sv) seq_felts += a.values.size();
+    const size_t o_step = o_col + (A + 3) / 4, o_val = o_step + (A + 3) / 4, o_sdesc = o_val + A,
+                 o_svals = o_sdesc + 3 * S, total = o_svals + seq_felts;
+    uint64_t strided_blocks = 0;
+    for (const airp::Strided& a : sv) strided_blocks += (n / a.stride + 63) / 64;
     felt* dimg = ctx->buf<felt>("check_image", total);
     std::vector<felt>& tag = ctx->host_cache["check_image_tag"];
-    const felt want = make((uint64_t)air_id, total);
+    const felt want = make((uint64_t)air_id | (S ? n << 32 : 0), total);
     if (tag.size() != 1 || !eq(tag[0], want)) {
       tag.clear();
       std::vector<felt> img(total, zero());
@@ -426,7 +442,20 @@ int zkp_air_check_trace_device(zkp_ctx* ctx, int air_id, const void* d_trace_col
         memcpy(img.data() + o_col, pr.a_col.data(), A * 4);
         memcpy(img.data() + o_val, pr.a_val.data(), A * 16);
       }
-      ctx->upload(dimg, img.data(), total * 16);  // at most 224 KiB: staged in the pinned ring
+      ProgStridedCells* cells = reinterpret_cast<ProgStridedCells*>(img.data() + o_sdesc);
+      uint32_t blk = 0, voff = 0;
+      for (size_t j = 0; j < S; j++) {
+        const uint32_t count = (uint32_t)(n / sv[j].stride);
+        cells[j] = ProgStridedCells{sv[j].col, (uint32_t)sv[j].first, (uint32_t)sv[j].stride, count, blk,
+                                    sv[j].sequence() ? voff : 0xffffffffu, {0, 0}, sv[j].val};
+        if (sv[j].sequence()) memcpy(img.data() + o_svals + voff, sv[j].values.data(), (size_t)count * 16);
+        voff += (uint32_t)sv[j].values.size();
+        blk += (count + 63) / 64;
+      }
+      // singles alone: at most 224 KiB, staged in the pinned ring. Sequence values can take it
+      // past the ring's 1 MiB (upload() then copies from `img` itself), so wait for that copy
+      ctx->upload(dimg, img.data(), total * 16);
+      if (total * 16 > (1u << 20)) ctx->sync();
       tag.assign(1, want);
     }
     ProgCheckArgs ca{};
@@ -441,9 +470,12 @@ int zkp_air_check_trace_device(zkp_ctx* ctx, int air_id, const void* d_trace_col
     ca.a_step = reinterpret_cast<const uint32_t*>(dimg + o_step);
     ca.a_val = dimg + o_val;
     ca.n = n;
+    ca.nstrided = (uint32_t)S;
+    ca.sdesc = reinterpret_cast<const ProgStridedCells*>(dimg + o_sdesc);
+    ca.svals = dimg + o_svals;
     unsigned long long* dres = ctx->buf<unsigned long long>("check_result", 2);
     HIP_CHECK(hipMemsetAsync(dres, 0xff, 16, ctx->stream));
-    launch_check_program(ctx->prof, ctx->stream, ca, width, (const felt*)d_trace_cols, dres);
+    launch_check_program(ctx->prof, ctx->stream, ca, width, (const felt*)d_trace_cols, dres, strided_blocks);
     unsigned long long res[2];
     ctx->download(res, dres, 16);  // the call's one stream synchronise
     ctx->collect_prof();
@@ -456,8 +488,8 @@ int zkp_air_check_trace_device(zkp_ctx* ctx, int air_id, const void* d_trace_col
       *bad_row = res[0] >> 10;
       *bad_constraint = (uint32_t)(res[0] & 1023);
     } else if (res[1] != ~0ull) {
-      *bad_row = pr.a_step[res[1]];
-      *bad_assertion = (uint32_t)res[1];
+      *bad_row = res[1] & 0xffffffffull;
+      *bad_assertion = (uint32_t)(res[1] >> 32);
     }
     return 0;
   });

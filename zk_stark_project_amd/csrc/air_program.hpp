@@ -24,8 +24,22 @@ inline uint32_t op_b(uint64_t op) { return (uint32_t)((op >> 32) & 0xffff); }
 inline uint32_t src_kind(uint32_t operand) { return operand >> 13; }
 inline uint32_t src_index(uint32_t operand) { return operand & 0x1fff; }
 
-// a registered program: the caller's arrays copied, the assertions sorted by (step, column)
+// a strided assertion (zkp_air_strided_assertion): T[col][first + stride*i] = val (periodic,
+// `values` empty) or values[i] (sequence)
+struct Strided {
+  uint32_t col = 0;
+  uint64_t first = 0, stride = 0;
+  felt val = {};
+  std::vector<felt> values;
+  bool sequence() const { return !values.empty(); }
+  felt value_at(uint64_t i) const { return values.empty() ? val : values[i]; }
+};
+
+// a registered program: the caller's arrays copied, the single assertions sorted by
+// (step, column), the strided ones by (stride, first, column)
 struct Program {
+  std::vector<Strided> strided;
+  size_t num_assertions() const { return a_col.size() + strided.size(); }
   uint32_t width = 0, num_t = 0, base_degree = 0, nreg = 0;
   std::vector<uint8_t> degrees;
   std::vector<felt> consts;
@@ -170,6 +184,67 @@ inline std::string validate(const zkp_air_program* p, Program& out) {
     rset[dst] = true;
   }
   if (emitted != p->num_constraints) return "ops: fewer EMITs than num_constraints";
+  return "";
+}
+
+// The strided assertions of zkp_air_register_strided against a program that validate()
+// has filled: every rule that does not depend on the trace length. Returns the empty
+// string, or a message naming strided[i].
+inline std::string validate_strided(const zkp_air_strided_assertion* s, uint32_t count, Program& out) {
+  auto idx = [](size_t i, const std::string& why) { return "strided[" + std::to_string(i) + "]: " + why; };
+  if (!count) return "";
+  if (!s) return "strided: null";
+  if ((uint64_t)count + out.a_col.size() > ZKP_AIR_MAX_ASSERTIONS)
+    return idx(ZKP_AIR_MAX_ASSERTIONS - out.a_col.size(), "more than 1024 assertions, single and strided together");
+  uint64_t seq_values = 0;
+  std::vector<uint32_t> order(count);
+  for (uint32_t i = 0; i < count; i++) {
+    order[i] = i;
+    const zkp_air_strided_assertion& a = s[i];
+    if (a.stride < 2 || (a.stride & (a.stride - 1))) return idx(i, "stride must be a power of two >= 2");
+    if (a.first_step >= a.stride) return idx(i, "first_step must be below the stride");
+    if (a.column >= out.width) return idx(i, "column outside the trace width");
+    if (a.num_values & (a.num_values - 1)) return idx(i, "num_values must be a power of two");
+    if (!a.num_values) {
+      if (ge_p(make(a.value.lo, a.value.hi))) return idx(i, "value not a canonical field element");
+      continue;
+    }
+    if (!a.values) return idx(i, "values: null");
+    seq_values += a.num_values;
+    if (seq_values > ZKP_AIR_MAX_SEQUENCE_VALUES) return idx(i, "more than 2^18 sequence values in the program");
+    for (uint32_t j = 0; j < a.num_values; j++)
+      if (ge_p(make(a.values[j].lo, a.values[j].hi)))
+        return idx(i, "values[" + std::to_string(j) + "] not a canonical field element");
+  }
+  // two assertions over one cell (independent of the trace length)
+  for (uint32_t i = 0; i < count; i++) {
+    for (uint32_t j = 0; j < i; j++) {
+      const uint64_t m = std::min(s[i].stride, s[j].stride);
+      if (s[i].column == s[j].column && (s[i].first_step & (m - 1)) == (s[j].first_step & (m - 1)))
+        return idx(i, "overlaps strided[" + std::to_string(j) + "]");
+    }
+    for (size_t k = 0; k < out.a_col.size(); k++)
+      if (out.a_col[k] == s[i].column && (out.a_step[k] & (s[i].stride - 1)) == s[i].first_step)
+        return idx(i, "overlaps the single assertion at step " + std::to_string(out.a_step[k]));
+  }
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+    const zkp_air_strided_assertion &a = s[x], &b = s[y];
+    if (a.stride != b.stride) return a.stride < b.stride;
+    return a.first_step != b.first_step ? a.first_step < b.first_step : a.column < b.column;
+  });
+  uint32_t groups = 0;
+  for (uint32_t k = 0; k < count; k++) {
+    const zkp_air_strided_assertion& a = s[order[k]];
+    if (!k || out.strided.back().stride != a.stride || out.strided.back().first != a.first_step) groups++;
+    if (groups > ZKP_AIR_MAX_STRIDED_GROUPS) return idx(order[k], "more than 4 distinct (stride, first_step) groups");
+    Strided d;
+    d.col = a.column;
+    d.first = a.first_step;
+    d.stride = a.stride;
+    d.val = a.num_values ? zero() : make(a.value.lo, a.value.hi);
+    for (uint32_t j = 0; j < a.num_values; j++) d.values.push_back(make(a.values[j].lo, a.values[j].hi));
+    out.strided.push_back(std::move(d));
+  }
   return "";
 }
 

@@ -187,6 +187,8 @@ struct AirDesc {
   std::vector<felt> a_val;
   felt k;
   std::shared_ptr<const airp::Program> prog;  // registered ids (zkp_air_register): the constraint program
+  // assertions = composition coefficients after the transition ones: the singles, then a program's strided ones
+  size_t num_assertions() const { return a_col.size() + (prog ? prog->strided.size() : 0); }
   uint32_t ce_blowup() const {
     uint32_t v = base_degree - 1, p = 1;
     while (p < v) p <<= 1;
@@ -256,6 +258,8 @@ inline int build_air(AirDesc& a, int id, uint32_t w, uint64_t n, const std::vect
     if (w != pr->width || pr->max_cycle() > n) return ZKP_ERR_PUB_INPUTS;
     for (uint64_t s : pr->a_step)
       if (s >= n) return ZKP_ERR_PUB_INPUTS;
+    for (const airp::Strided& s : pr->strided)
+      if (s.stride > n || (s.sequence() && s.values.size() * s.stride != n)) return ZKP_ERR_PUB_INPUTS;
     // A constraint of degree d over n rows has a quotient of degree (d-1)(n-1), and comp_cols()
     // (winterfell's count) provides ceil((d-1)(n-1)/n) columns of n coefficients: one short
     // exactly when n divides d-1. No proof of such a shape verifies.
@@ -322,7 +326,7 @@ inline std::vector<felt> context_elements(const AirDesc& a, const zkp_proof_opti
   e.push_back(felt_u64((uint32_t)a.n));
   e.push_back(felt_u64(0xffffd30000000001ULL));
   e.push_back(felt_u64(0xffffffffffffffffULL));
-  e.push_back(felt_u64(a.num_t + a.a_col.size()));
+  e.push_back(felt_u64(a.num_t + a.num_assertions()));
   uint32_t buf = o->field_extension;
   buf = (buf << 8) | o->fri_folding_factor;
   buf = (buf << 8) | o->fri_remainder_max_degree;
@@ -339,7 +343,7 @@ inline void write_context(Writer& w, const AirDesc& a, const zkp_proof_options* 
   w.u8((uint8_t)o->num_queries); w.u8((uint8_t)o->blowup_factor); w.u8((uint8_t)o->grinding_factor);
   w.u8((uint8_t)o->field_extension); w.u8((uint8_t)o->fri_folding_factor); w.u8((uint8_t)o->fri_remainder_max_degree);
   w.u8((uint8_t)o->batching_constraints); w.u8((uint8_t)o->batching_deep);
-  w.u32((uint32_t)(a.num_t + a.a_col.size()));
+  w.u32((uint32_t)(a.num_t + a.num_assertions()));
 }
 
 // MerkleTree::prove_batch plan: emission order of (path slot, node index).

@@ -463,6 +463,105 @@ __global__ __launch_bounds__(PROG_TPB) void k_eval_program(EvalCommon c, ProgEva
   comp[q] = v;
 }
 
+// k_eval_program written out again for a program with strided assertions (ProgStridedArgs): the
+// same interpreter and single-step groups, then the strided groups. A program without them
+// launches k_eval_program, whose code is what it was before they existed.
+__global__ __launch_bounds__(PROG_TPB) void k_eval_program_strided(EvalCommon c, ProgEvalArgs a, ProgStridedArgs sa,
+                                                                   const felt* __restrict__ lde,
+                                                                   felt* __restrict__ comp) {
+  extern __shared__ __align__(16) unsigned char prog_lds[];
+  // register r of this lane: rg[r * PROG_TPB]. The pointer keeps its LDS address space, so
+  // a register operand is a ds_read_b128 and never merges with the global loads into a flat one
+  lds_u32x4* const rg = (lds_u32x4*)prog_lds + threadIdx.x;
+  const uint64_t M = (uint64_t)c.cel << c.logn;
+  const uint64_t q = (uint64_t)blockIdx.x * PROG_TPB + threadIdx.x;
+  if (q >= M) return;
+  const CePoint pt = ce_point(c, q);
+  const felt* const cur = lde + pt.off;
+  const felt* const nxt = lde + pt.off_next;
+  auto fetch = [&](uint32_t operand) -> felt {
+    const uint32_t idx = operand & 0x1fff;
+    switch (operand >> 13) {
+      case ZKP_SRC_REG: {
+        const u32x4 r = rg[idx * PROG_TPB];
+        return make((uint64_t)r.x | ((uint64_t)r.y << 32), (uint64_t)r.z | ((uint64_t)r.w << 32));
+      }
+      case ZKP_SRC_CUR: return cur[idx * a.col_stride];
+      case ZKP_SRC_NEXT: return nxt[idx * a.col_stride];
+      case ZKP_SRC_PERIODIC: {
+        const ProgPeriodic d = a.per_desc[idx];
+        return a.per_tab[d.off + ((uint32_t)pt.s & d.mask)];
+      }
+      default: return a.consts[idx];
+    }
+  };
+  // transition part: T = sum_i cc[i] * t_i (an EMIT is a product with its coefficient)
+  felt T = zero();
+  uint32_t emitted = 0;
+  for (uint32_t pc = 0; pc < a.nops; pc++) {
+    const uint64_t op = a.ops[pc];
+    const uint32_t code = (uint32_t)op & 0xff;
+    const felt x = fetch((uint32_t)(op >> 16) & 0xffff);
+    const felt y = code == ZKP_OP_EMIT ? a.cc[emitted] : fetch((uint32_t)(op >> 32) & 0xffff);
+    felt r;
+    if (code == ZKP_OP_ADD) r = add(x, y);
+    else if (code == ZKP_OP_SUB) r = sub(x, y);
+    else r = mul(x, y);
+    if (code == ZKP_OP_EMIT) {
+      T = add(T, r);
+      emitted++;
+    } else {
+      u32x4 w;
+      w.x = (uint32_t)r.lo; w.y = (uint32_t)(r.lo >> 32); w.z = (uint32_t)r.hi; w.w = (uint32_t)(r.hi >> 32);
+      rg[((uint32_t)(op >> 8) & 0xff) * PROG_TPB] = w;
+    }
+  }
+  const felt px = point_x(c.pm, q);
+  felt v = mul(mul(T, sub(px, c.w_last)), c.zinv[pt.u]);
+  // boundary part, one divisor table per group of assertions that share a step
+  const felt* const bcc = a.cc + a.num_t;
+  uint32_t k = 0;
+  static_for<0, (int)PROG_MAX_GROUPS>([&](auto g) {
+    if ((uint32_t)g < a.ngroups) {
+      felt s = zero();
+      for (; k < a.grp_end[g]; k++) s = add(s, mul(bcc[k], sub(cur[a.a_col[k] * a.col_stride], a.a_val[k])));
+      v = add(v, mul(s, a.dinv[g][q]));
+    }
+  });
+  // strided groups: sum_k cc_k (cur[col_k] - val_k) - W_g, W_g = sum over the group's sequences of
+  // cc_j V_j (k_strided_combine, extended to the CE cosets), over x^k - w^(first k): a table of
+  // stride * ce inverses read at the CE index modulo its length, as the periodic columns are
+  uint32_t j = 0;
+  static_for<0, (int)PROG_MAX_STRIDED_GROUPS>([&](auto g) {
+    if ((uint32_t)g < sa.ngroups) {
+      felt s = zero();
+      for (; j < sa.grp_end[g]; j++) s = add(s, mul(sa.cc[j], sub(cur[sa.col[j] * a.col_stride], sa.val[j])));
+      if (sa.W[g]) s = sub(s, sa.W[g][q]);
+      v = add(v, mul(s, sa.dtab[g][(uint32_t)pt.s & sa.mask[g]]));
+    }
+  });
+  comp[q] = v;
+}
+
+// W_g = sum_j cc_j V_j over the sequences j of strided group g = blockIdx.y, as one coefficient
+// column in the library's layout: position p holds n * w_{rev(p)} (bit-reversed, n-scaled; tab
+// holds the twisted coefficients of every V_j already multiplied by n), zero from degree k up.
+// The descriptors and coefficients are uniform loads.
+__global__ __launch_bounds__(TPB) void k_strided_combine(ProgSeqArgs a, uint32_t logn, felt* __restrict__ out) {
+  const uint32_t g = blockIdx.y;
+  const uint64_t n = 1ull << logn;
+  const uint64_t p = (uint64_t)blockIdx.x * TPB + threadIdx.x;
+  if (p >= n) return;
+  const uint32_t i = rev_bits((uint32_t)p, logn);
+  felt s = zero();
+  if (i < (1u << a.logk[g]))
+    for (uint32_t d = g ? a.seq_end[g - 1] : 0; d < a.seq_end[g]; d++) {
+      const ProgSeq q = a.desc[d];
+      s = add(s, mul(a.cc[q.cc], a.tab[q.off + i]));
+    }
+  out[(uint64_t)g * n + p] = s;
+}
+
 // A natural (column-major, not extended) trace against a registered constraint
 // program: what zkp_air_check_trace does on the host. Blocks [0, frame_blocks) take one
 // frame (rows r, r + 1) per thread, r in [0, n - 2]: row n - 1 starts no frame and nothing
@@ -475,17 +574,45 @@ __global__ __launch_bounds__(PROG_TPB) void k_eval_program(EvalCommon c, ProgEva
 // stream is wave-uniform). Keys (r << 10) | constraint grow with the lane, so the
 // wave's minimum is the key of its lowest failing lane (one ballot); that lane alone
 // does a 64-bit atomicMin on res[0]. A valid trace issues no atomic.
-// The blocks after them check the assertions, thread k the stored assertion k, with the
-// same ballot and an atomicMin of k on res[1].
+// The blocks after them check the assertions, one thread per asserted cell: thread k the
+// stored single assertion k, then every strided assertion over blocks of its own (cell i
+// of it is row first + stride * i). Same ballot; the key (assertion index << 32) | row
+// grows with the lane too, and the lowest failing lane does an atomicMin on res[1], so the
+// host reads the first failing assertion in stored order and its lowest failing row.
 __global__ __launch_bounds__(PROG_TPB) void k_check_program(ProgCheckArgs a, const felt* __restrict__ T,
                                                             unsigned long long* __restrict__ res) {
   extern __shared__ __align__(16) unsigned char check_lds[];
   if (blockIdx.x >= a.frame_blocks) {
-    const uint32_t k = (blockIdx.x - a.frame_blocks) * PROG_TPB + threadIdx.x;
-    if (k >= a.nassert) return;
-    const bool fail = !eq(T[(uint64_t)a.a_col[k] * a.n + a.a_step[k]], a.a_val[k]);
+    const uint32_t ab = blockIdx.x - a.frame_blocks;
+    bool fail = false;
+    unsigned long long key = 0;
+    if (ab < a.single_blocks) {
+      const uint32_t k = ab * PROG_TPB + threadIdx.x;
+      if (k < a.nassert) {
+        fail = !eq(T[(uint64_t)a.a_col[k] * a.n + a.a_step[k]], a.a_val[k]);
+        key = ((unsigned long long)k << 32) | a.a_step[k];
+      }
+    } else {
+      // the strided assertion whose run of blocks holds this one: the largest j with
+      // blk0[j] <= sb (block-uniform, so the search is scalar loads and branches)
+      const uint32_t sb = ab - a.single_blocks;
+      uint32_t lo = 0, hi = a.nstrided;
+      while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) / 2;
+        if (a.sdesc[mid].blk0 <= sb) lo = mid;
+        else hi = mid;
+      }
+      const ProgStridedCells d = a.sdesc[lo];
+      const uint32_t i = (sb - d.blk0) * PROG_TPB + threadIdx.x;
+      if (i < d.count) {
+        const uint64_t row = d.first + (uint64_t)d.stride * i;
+        const felt want = d.voff != 0xffffffffu ? a.svals[d.voff + i] : d.val;
+        fail = !eq(T[(uint64_t)d.col * a.n + row], want);
+        key = ((unsigned long long)(a.nassert + lo) << 32) | row;
+      }
+    }
     const uint64_t failing = __builtin_amdgcn_ballot_w64(fail);
-    if (failing && threadIdx.x == (uint32_t)__builtin_ctzll(failing)) atomicMin(res + 1, (unsigned long long)k);
+    if (failing && threadIdx.x == (uint32_t)__builtin_ctzll(failing)) atomicMin(res + 1, key);
     return;
   }
   lds_u32x4* const rg = (lds_u32x4*)check_lds + threadIdx.x;
@@ -1435,7 +1562,7 @@ void launch_eval_mimc(Prof& prof, hipStream_t s, const EvalCommon& c, const Mimc
 }
 
 void launch_eval_program(Prof& prof, hipStream_t s, const EvalCommon& c, const ProgEvalArgs& a, const felt* lde,
-                         felt* comp) {
+                         felt* comp, const ProgStridedArgs* sa) {
   const uint64_t M = (uint64_t)c.cel << c.logn;
   if (a.nreg == 0 || a.nreg > ZKP_AIR_MAX_REGISTERS || a.ngroups > PROG_MAX_GROUPS)
     launch_fail(ZKP_ERR_ARGUMENT, "constraint program outside the kernel's limits");
@@ -1443,17 +1570,42 @@ void launch_eval_program(Prof& prof, hipStream_t s, const EvalCommon& c, const P
     if (!a.dinv_ready[g]) launch_den_table(prof, s, c.pm, M, a.w_step[g], zero(), 0, a.binv, a.dinv[g]);
   // LDS: the program's registers, [register][thread] (16 bytes per lane)
   const size_t lds = (size_t)a.nreg * PROG_TPB * sizeof(felt);
+  if (sa && sa->ngroups) {
+    if (sa->ngroups > PROG_MAX_STRIDED_GROUPS)
+      launch_fail(ZKP_ERR_ARGUMENT, "constraint program outside the kernel's limits");
+    LAUNCH(prof, "eval_program_strided", s, (double)M * 48.0,
+           hipLaunchKernelGGL(k_eval_program_strided, dim3(blocks_for(M, PROG_TPB)), dim3(PROG_TPB), lds, s, c, a, *sa,
+                              lde, comp));
+    return;
+  }
   LAUNCH(prof, "eval_program", s, (double)M * 48.0,
          hipLaunchKernelGGL(k_eval_program, dim3(blocks_for(M, PROG_TPB)), dim3(PROG_TPB), lds, s, c, a, lde, comp));
 }
 
+void launch_strided_den_table(Prof& prof, hipStream_t s, const felt* gk, const felt* twl, uint32_t logl, felt c0,
+                              felt* scratch, felt* table) {
+  // the three phases of the single-step tables over the one "coset" gk * <w_l>, in natural order
+  launch_den_table(prof, s, PointMap{gk, twl, logl}, 1ull << logl, c0, zero(), 0, scratch, table);
+}
+
+void launch_strided_combine(Prof& prof, hipStream_t s, const ProgSeqArgs& a, uint32_t logn, felt* out) {
+  if (!a.ngroups || a.ngroups > PROG_MAX_STRIDED_GROUPS)
+    launch_fail(ZKP_ERR_ARGUMENT, "constraint program outside the kernel's limits");
+  LAUNCH(prof, "strided_combine", s, (double)a.ngroups * (double)(1ull << logn) * 16.0,
+         hipLaunchKernelGGL(k_strided_combine, dim3(blocks_for(1ull << logn), a.ngroups), dim3(TPB), 0, s, a, logn,
+                            out));
+}
+
 void launch_check_program(Prof& prof, hipStream_t s, ProgCheckArgs a, uint32_t width, const felt* T,
-                          unsigned long long* res) {
+                          unsigned long long* res, uint64_t strided_blocks) {
   if (a.nreg == 0 || a.nreg > ZKP_AIR_MAX_REGISTERS || a.nassert > ZKP_AIR_MAX_ASSERTIONS || a.n < 2 ||
       a.n > (1ull << MAX_LOG_TRACE))
     launch_fail(ZKP_ERR_ARGUMENT, "trace check outside the kernel's limits");
   a.frame_blocks = blocks_for(a.n - 1, PROG_TPB);
-  const uint32_t blocks = a.frame_blocks + blocks_for(a.nassert, PROG_TPB);
+  a.single_blocks = blocks_for(a.nassert, PROG_TPB);
+  const uint64_t all = (uint64_t)a.frame_blocks + a.single_blocks + strided_blocks;
+  if (all >> 31) launch_fail(ZKP_ERR_ARGUMENT, "trace check outside the kernel's limits");
+  const uint32_t blocks = (uint32_t)all;
   const size_t lds = (size_t)a.nreg * PROG_TPB * sizeof(felt);
   LAUNCH(prof, "check_program", s, (double)width * (double)a.n * 16.0,
          hipLaunchKernelGGL(k_check_program, dim3(blocks), dim3(PROG_TPB), lds, s, a, T, res));

@@ -70,7 +70,7 @@ void ProofRun::setup() {
   // device transcript: the coin state lives in HBM from here until
   // the OOD download; the device draws the composition coefficients and z, the
   // host replays both draws from the downloaded roots and checks them
-  ncoef = air.num_t + (uint32_t)air.a_col.size();
+  ncoef = air.num_t + (uint32_t)air.num_assertions();
   dt_seed = ctx->buf<uint32_t>("dt_seed", 8);
   dt_cc = ctx->buf<felt>("dt_cc", ncoef);
   dt_zz = ctx->buf<felt>("dt_zz", 2);

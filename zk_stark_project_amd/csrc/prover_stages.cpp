@@ -152,6 +152,18 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
   if (!ctx->have_cached(zkey)) ctx->upload(dz, zinv.data(), ce * 16);
   const std::string dom = std::to_string(logn) + "_" + std::to_string(logB) + "_" + std::to_string(u0) + "_" +
                           std::to_string(cel);
+  // the coset-scale rows of the CE cosets (LDE cosets u * B/ce), gathered into one table per
+  // (n, B, ce), cached: what extends a coefficient column to the CE cosets
+  auto sce_rows = [&]() -> const felt* {
+    const uint32_t cstep = logB - logce;
+    const felt* S = ctx->S(logn, logB);
+    if (!cstep) return S;
+    const std::string skey = "Sce_" + std::to_string(logn) + "_" + std::to_string(logB) + "_" + std::to_string(logce);
+    felt* t = ctx->buf<felt>(skey, (size_t)ce * n);
+    if (!ctx->have_cached(skey))
+      HIP_CHECK(hipMemcpy2DAsync(t, n * 16, S, (n << cstep) * 16, n * 16, ce, hipMemcpyDeviceToDevice, st));
+    return t;
+  };
   if (air.prog) {
     // a registered constraint program: k_eval_program reads the coefficients from dt_cc as drawn
     if (!cel) return;
@@ -163,10 +175,20 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
     // Periodic column of cycle c over the CE domain: interpolate over <w_c>, evaluate at
     // g^(n/c) * <w_{c ce}> (as kper_* below), indexed by the CE index mod c*ce.
     const size_t P = pr.periodic.size();
+    // Strided assertions append [columns | values | sequence descriptors | sequence tables]:
+    // per sequence the k coefficients of V_j, interpolated over <w_k>, twisted by
+    // w_n^(-first i) and multiplied by n (the coefficient layout k_strided_combine writes).
+    const std::vector<airp::Strided>& sv = pr.strided;
+    const size_t S = sv.size();
+    size_t nseq = 0, seq_felts = 0;
+    for (const airp::Strided& a : sv)
+      if (a.sequence()) nseq++, seq_felts += a.values.size();
     const size_t o_ops = 0, o_const = o_ops + (pr.ops.size() + 1) / 2, o_col = o_const + pr.consts.size(),
                  o_desc = o_col + (pr.a_col.size() + 3) / 4, o_tab = o_desc + (P + 1) / 2;
-    size_t total = o_tab;
-    for (const auto& col : pr.periodic) total += col.size() * ce;
+    size_t o_scol = o_tab;
+    for (const auto& col : pr.periodic) o_scol += col.size() * ce;
+    const size_t o_sval = o_scol + (S + 3) / 4, o_sdesc = o_sval + S, o_stab = o_sdesc + (nseq + 1) / 2,
+                 total = o_stab + seq_felts;
     felt* dimg = ctx->buf<felt>("prog_image", total);
     std::vector<felt>& img = ctx->host_cache["prog_image"];  // kept: a large image is copied from it asynchronously
     std::vector<felt>& tag = ctx->host_cache["prog_image_tag"];
@@ -187,6 +209,24 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
         memcpy(img.data() + o_tab + off, kv.data(), kv.size() * 16);
         desc[p] = ProgPeriodic{(uint32_t)off, (uint32_t)(cyc * ce - 1)};
         off += kv.size();
+      }
+      uint32_t* scol = reinterpret_cast<uint32_t*>(img.data() + o_scol);
+      ProgSeq* sdesc = reinterpret_cast<ProgSeq*>(img.data() + o_sdesc);
+      size_t soff = 0, q = 0;
+      for (size_t j = 0; j < S; j++) {
+        scol[j] = sv[j].col;
+        img[o_sval + j] = sv[j].val;
+        if (!sv[j].sequence()) continue;
+        std::vector<felt> pc = sv[j].values;
+        host_interpolate(pc, one());
+        const felt tw = inv(pow_u64(wn, sv[j].first));
+        felt sc = felt_u64(n);
+        for (size_t i = 0; i < pc.size(); i++) {
+          img[o_stab + soff + i] = mul(pc[i], sc);
+          sc = mul(sc, tw);
+        }
+        sdesc[q++] = ProgSeq{(uint32_t)j, (uint32_t)soff};
+        soff += pc.size();
       }
       ctx->upload(dimg, img.data(), total * 16);
       tag.assign(want, want + 2);
@@ -218,7 +258,62 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
       }
       pa.grp_end[pa.ngroups - 1] = (uint32_t)k + 1;
     }
-    launch_eval_program(pf, st, ec, pa, tlde, comp);
+    if (!S) {
+      launch_eval_program(pf, st, ec, pa, tlde, comp);
+      return;
+    }
+    ProgStridedArgs sa{};
+    ProgSeqArgs qa{};
+    sa.col = reinterpret_cast<const uint32_t*>(dimg + o_scol);
+    sa.val = dimg + o_sval;
+    sa.cc = qa.cc = dt_cc + pr.num_t + pr.a_col.size();
+    qa.desc = reinterpret_cast<const ProgSeq*>(dimg + o_sdesc);
+    qa.tab = dimg + o_stab;
+    int wslot[PROG_MAX_STRIDED_GROUPS] = {-1, -1, -1, -1};  // the group's column of W, if it holds a sequence
+    uint32_t seqs = 0;
+    for (size_t j = 0; j < S; j++) {
+      const uint64_t k = n / sv[j].stride, len = sv[j].stride * ce;
+      if (j == 0 || sv[j].stride != sv[j - 1].stride || sv[j].first != sv[j - 1].first) {
+        if (sa.ngroups == PROG_MAX_STRIDED_GROUPS)
+          throw ZkpFail{ZKP_ERR_UNSUPPORTED_AIR, "strided assertions over more than 4 groups"};
+        const uint32_t gi = sa.ngroups++;
+        sa.mask[gi] = (uint32_t)(len - 1);
+        // 1/(x^k - w_n^(first k)) by CE index modulo stride * ce: x^k = g^k w_len^s. Domain-only:
+        // built once per (n, ce, stride, first) by the batch inversion of the single-step
+        // tables; g^k sits behind the table for the kernels to read
+        const std::string key = "dstr_" + std::to_string(logn) + "_" + std::to_string(logce) + "_" +
+                                std::to_string(sv[j].stride) + "_" + std::to_string(sv[j].first);
+        felt* tab = ctx->buf<felt>(key, len + 1);
+        if (!ctx->have_cached(key)) {
+          const felt gk = pow_u64(g, k);
+          ctx->upload(tab + len, &gk, 16);
+          launch_strided_den_table(pf, st, tab + len, ctx->tws(logN) + (len / 2 - 1), ilog2(len),
+                                   pow_u64(wn, sv[j].first * k), pa.binv, tab);
+        }
+        sa.dtab[gi] = tab;
+      }
+      const uint32_t gi = sa.ngroups - 1;
+      sa.grp_end[gi] = (uint32_t)j + 1;
+      if (sv[j].sequence()) {
+        if (wslot[gi] < 0) {
+          wslot[gi] = (int)qa.ngroups++;
+          qa.logk[wslot[gi]] = ilog2(k);
+        }
+        qa.seq_end[wslot[gi]] = ++seqs;
+      }
+    }
+    if (qa.ngroups) {
+      // W_g for the groups that hold a sequence: combined from the coefficients as drawn, then
+      // extended to the CE cosets like the linear AIRs' combined columns (no host round trip)
+      felt* wc = ctx->buf<felt>("strided_w_coef", (size_t)qa.ngroups * n);
+      felt* wev = ctx->buf<felt>("strided_w_ev", (size_t)qa.ngroups * cel * n);
+      launch_strided_combine(pf, st, qa, logn, wc);
+      NttBatch eb{wc, wev, sce_rows() + (uint64_t)u0 * n, n, n, cel, cel, qa.ngroups * cel};
+      launch_ntt(pf, st, eb, logn, true, ctx->tws(logN), logN);
+      for (uint32_t gi = 0; gi < sa.ngroups; gi++)
+        if (wslot[gi] >= 0) sa.W[gi] = wev + (size_t)wslot[gi] * cel * n;
+    }
+    launch_eval_program(pf, st, ec, pa, tlde, comp, &sa);
     return;
   }
   // coefficient-dependent constants, built on the device from the drawn coefficients
@@ -250,18 +345,8 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
                        dconst, twn, mine, part);
     for (uint32_t i = 0; R > 1 && i < narr; i++) cm->all_gather(st, mine + i * nR, lc + i * n, nR * 16);
     if (!cel) return;
-    // extend to the CE cosets u0..u0+cel (LDE cosets u*B/ce): their coset-scale rows
-    // gathered into one table per (n, B, ce), cached
-    const uint32_t cstep = logB - logce;
-    const std::string skey = "Sce_" + std::to_string(logn) + "_" + std::to_string(logB) + "_" + std::to_string(logce);
-    const felt* S = ctx->S(logn, logB);
-    const felt* Sce = S;
-    if (cstep) {
-      felt* t = ctx->buf<felt>(skey, (size_t)ce * n);
-      if (!ctx->have_cached(skey))
-        HIP_CHECK(hipMemcpy2DAsync(t, n * 16, S, (n << cstep) * 16, n * 16, ce, hipMemcpyDeviceToDevice, st));
-      Sce = t;
-    }
+    // extend to the CE cosets u0..u0+cel
+    const felt* Sce = sce_rows();
     felt* ev = ctx->buf<felt>("lin_ev", (size_t)narr * cel * n);
     NttBatch eb{lc, ev, Sce + (uint64_t)u0 * n, n, n, cel, cel, narr * cel};
     launch_ntt(pf, st, eb, logn, true, ctx->tws(logN), logN);

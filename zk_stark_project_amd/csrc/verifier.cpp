@@ -253,7 +253,7 @@ int verify_impl(int air_id, const uint8_t* proof, uint64_t len, const zkp_felt* 
   for (uint64_t i = 0; i < n_pub; i++) pub[i] = make(pub_elems[i].lo, pub_elems[i].hi);
   AirDesc air;
   if (build_air(air, air_id, w, n, pub) != 0) return ZKP_VERIFY_PUB_INPUTS;
-  if (num_constraints != air.num_t + air.a_col.size()) return ZKP_VERIFY_DESERIALIZATION;
+  if (num_constraints != air.num_t + air.num_assertions()) return ZKP_VERIFY_DESERIALIZATION;
   const uint32_t C = air.comp_cols();
   const uint32_t L = fri_num_layers(N, &o);
   // ---- commitments, queries, OOD frame, FRI proof, nonce
@@ -307,6 +307,27 @@ int verify_impl(int air_id, const uint8_t* proof, uint64_t len, const zkp_felt* 
     for (size_t i = 0; i < air.a_col.size(); i++) {
       felt num = sub(ood_trace[air.a_col[i]], air.a_val[i]);
       lhs = add(lhs, mul(mul(cc[air.num_t + i], num), inv(sub(z, pow_u64(wn, air.a_step[i])))));
+    }
+    // a program's strided assertions (include/zkp.h): per group (stride, first) the divisor
+    // z^k - w_n^(first k), k = n / stride; V_j(z) = value, or the sequence's interpolant at z w_n^-first
+    if (air.prog) {
+      const auto& st = air.prog->strided;
+      felt dinv = zero(), zs = zero();
+      for (size_t j = 0; j < st.size(); j++) {
+        const uint64_t k = n / st[j].stride;
+        if (!j || st[j].stride != st[j - 1].stride || st[j].first != st[j - 1].first) {
+          dinv = inv(sub(pow_u64(z, k), pow_u64(wn, st[j].first * k)));
+          zs = mul(z, inv(pow_u64(wn, st[j].first)));
+        }
+        felt v = st[j].val;
+        if (st[j].sequence()) {
+          std::vector<felt> p = st[j].values;
+          host_interpolate(p, one());
+          v = horner(p, zs);
+        }
+        const felt num = sub(ood_trace[st[j].col], v);
+        lhs = add(lhs, mul(mul(cc[air.num_t + air.a_col.size() + j], num), dinv));
+      }
     }
     felt rhs = zero(), zp = one();
     for (uint32_t j = 0; j < C; j++) {
@@ -467,6 +488,18 @@ extern "C" int zkp_air_check_trace(int air_id, const zkp_felt* trace_cols, uint3
         *bad_row = pr.a_step[k];
         *bad_assertion = (uint32_t)k;
         return ZKP_OK;
+      }
+    }
+    for (size_t j = 0; j < pr.strided.size(); j++) {
+      const airp::Strided& s = pr.strided[j];
+      for (uint64_t i = 0; i < n / s.stride; i++) {
+        const uint64_t r = s.first + s.stride * i;
+        const zkp_felt e = trace_cols[(size_t)s.col * n + r];
+        if (!eq(make(e.lo, e.hi), s.value_at(i))) {
+          *bad_row = r;
+          *bad_assertion = (uint32_t)(pr.a_col.size() + j);
+          return ZKP_OK;
+        }
       }
     }
     return ZKP_OK;

@@ -300,16 +300,63 @@ struct ProgEvalArgs {
   bool dinv_ready[PROG_MAX_GROUPS];
   felt* binv;            // scratch: one felt per 2048 CE points
 };
+// A program's strided assertions (include/zkp.h zkp_air_strided_assertion), in stored order
+// (stride, first, column); a group shares (stride, first) and the divisor x^k - w_n^(first k),
+// k = n / stride. k_eval_program_strided adds, per group,
+//   (sum_j cc_j * (cur[col_j] - val_j) - W_g[q]) * dtab_g[CE index & mask_g]
+// after the single-step groups: val_j = 0 for a sequence, whose values enter through
+// W_g = sum_j cc_j V_j (launch_strided_combine, then the coset NTT), null for a group of
+// periodic assertions alone.
+constexpr uint32_t PROG_MAX_STRIDED_GROUPS = 4;  // ZKP_AIR_MAX_STRIDED_GROUPS
+struct ProgStridedArgs {
+  uint32_t ngroups;
+  uint32_t grp_end[PROG_MAX_STRIDED_GROUPS];  // strided assertions [grp_end[g-1], grp_end[g]) form group g
+  uint32_t mask[PROG_MAX_STRIDED_GROUPS];     // stride * ce - 1
+  const felt* dtab[PROG_MAX_STRIDED_GROUPS];  // stride * ce felts: 1/(x^k - w_n^(first k)) by CE index (cached in the ctx)
+  const felt* W[PROG_MAX_STRIDED_GROUPS];     // cel * n felts: W_g over the shard's CE points, or null
+  const uint32_t* col;   // device: the strided assertions' columns
+  const felt* val;       // device: their values (zero for a sequence)
+  const felt* cc;        // device: the coefficient of the first strided assertion
+};
+// `sa` (nullable): with strided groups the launch is k_eval_program_strided
 void launch_eval_program(Prof& prof, hipStream_t s, const EvalCommon& c, const ProgEvalArgs& a, const felt* lde,
-                         felt* comp);
+                         felt* comp, const ProgStridedArgs* sa = nullptr);
+// table[s] = 1/(gk[0] * w_l^s - c0) for s < l = 2^logl (gk: one device felt, g^k; twl[j] = w_l^j,
+// j < l/2): the phases of the single-step tables, one field inversion. scratch: l / 2048 + 1 felts
+void launch_strided_den_table(Prof& prof, hipStream_t s, const felt* gk, const felt* twl, uint32_t logl, felt c0,
+                              felt* scratch, felt* table);
+// W_g's coefficient column for every group that holds a sequence (k_strided_combine):
+// out[g * n + p] = sum_d cc[desc[d].cc] * tab[desc[d].off + rev(p)] for rev(p) < 2^logk[g], else 0
+struct ProgSeq {
+  uint32_t cc, off;      // a sequence: its coefficient cc[cc]; its 2^logk n-scaled, twisted coefficients at tab + off
+};
+struct ProgSeqArgs {
+  uint32_t ngroups;                          // groups that hold a sequence
+  uint32_t seq_end[PROG_MAX_STRIDED_GROUPS]; // sequences [seq_end[g-1], seq_end[g]) of desc belong to group g
+  uint32_t logk[PROG_MAX_STRIDED_GROUPS];
+  const ProgSeq* desc;   // device
+  const felt* tab;       // device
+  const felt* cc;        // device: the coefficient of the first strided assertion
+};
+void launch_strided_combine(Prof& prof, hipStream_t s, const ProgSeqArgs& a, uint32_t logn, felt* out);
 
 // The natural trace T (column-major, width x n) against a registered program
 // (k_check_program; zkp_air_check_trace_device): one frame per thread, then the
 // assertions. res[0] (preset to UINT64_MAX) receives the minimum (row << 10) | constraint
-// over the failing frames, res[1] the minimum index of a failing assertion.
+// over the failing frames, res[1] the minimum (assertion index << 32) | row over the failing
+// asserted cells (singles first, then the strided assertions, cell by cell).
+struct ProgStridedCells {
+  uint32_t col, first, stride, count;  // cells T[col][first + stride * i], i < count = n / stride
+  uint32_t blk0, voff;   // first of its blocks among the strided ones; values at svals + voff, or 0xffffffff: val
+  uint32_t pad[2];
+  felt val;
+};
 struct ProgCheckArgs {
   const uint64_t* ops;   // device: the op stream
-  uint32_t nops, nreg, nassert, frame_blocks;  // frame_blocks: set by the launcher
+  uint32_t nops, nreg, nassert, frame_blocks;  // nassert: the singles; frame_blocks: set by the launcher
+  uint32_t single_blocks, nstrided;            // single_blocks: set by the launcher
+  const ProgStridedCells* sdesc;  // device: one per strided assertion, in stored order
+  const felt* svals;     // device: the sequences' values
   const felt* consts;    // device: the constant pool
   const ProgPeriodic* per_desc;  // device: one per periodic column, mask = cycle - 1
   const felt* per_tab;   // device: the periodic columns' raw values, indexed by (row & mask)
@@ -318,8 +365,9 @@ struct ProgCheckArgs {
   const felt* a_val;
   uint64_t n;            // 2 <= n <= 2^MAX_LOG_TRACE
 };
+// strided_blocks: the blocks of the strided assertions (sum of ceil(count / 64))
 void launch_check_program(Prof& prof, hipStream_t s, ProgCheckArgs a, uint32_t width, const felt* T,
-                          unsigned long long* res);
+                          unsigned long long* res, uint64_t strided_blocks = 0);
 
 // GlobalUpdate column pairing (kernels.hip): columns d+i from columns i < d for a
 // trace whose transitions hold. check: rows [t0, t0 + 2^logtn) of pairs c0..c0+cw of
