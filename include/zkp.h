@@ -448,7 +448,14 @@ int zkp_eval_constraints(zkp_session* s, const zkp_felt* coeffs, uint32_t n_coef
  * evals = NULL: the session's zkp_eval_constraints output; otherwise n*ce host values in
  * natural CE-domain order (e.g. from a CPU evaluator). num_columns (nullable) = C. */
 int zkp_composition_commit(zkp_session* s, const zkp_felt* evals, uint8_t root[32], uint32_t* num_columns);
-/* OOD frame at z: trace_ood[0..w) = T(z), trace_ood[w..2w) = T(z*w_n); comp_ood[0..C) = H_j(z). */
+/* OOD frame at z: trace_ood[0..w) = T(z), trace_ood[w..2w) = T(z*w_n); comp_ood[0..C) = H_j(z).
+ * z is any canonical element (< p) off the LDE domain: with N = n * blowup, a z with
+ * z^N = 3^N has z or z*w_n on the coset 3*<w_N>, where zkp_deep_fri divides by
+ * (x - z)(x - z*w_n) at every point x, and is refused with ZKP_ERR_ARGUMENT before
+ * anything is launched (the session stays at this stage and takes another z). A point
+ * of the trace domain (z = w_n^k) is accepted: the frame is then rows k and k + 1 of
+ * the trace. Every challenge of the stage entry points (composition and DEEP
+ * coefficients, z, FRI alphas) must be canonical; one >= p is ZKP_ERR_ARGUMENT. */
 int zkp_ood_frame(zkp_session* s, zkp_felt z, zkp_felt* trace_ood, zkp_felt* comp_ood);
 /* Called once per FRI layer with its Merkle root; returns that layer's alpha in *alpha
  * (a fork binds it to `channel.commit_fri_layer(root); channel.draw_fri_alpha()`); non-zero aborts. */

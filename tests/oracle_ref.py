@@ -184,35 +184,81 @@ class Stages(ctypes.Structure):
                 ("pad", ctypes.c_uint32)]
 
 
-def prove_stages(air_id: int, trace_cols: bytes, width: int, n: int, pub: bytes, opts, ce: int, C: int):
-    """Oracle proof + its stage values: dict of byte strings (16 B LE felts) keyed
-    coeffs, comp_evals (n*ce, natural CE order), ood (2w + C), deep_coeffs (w + C),
-    alphas (one per FRI layer), remainder."""
+class Queries(ctypes.Structure):
+    """oracle_queries (oracle/stark_oracle.c): z, the query positions and the nonce of one oracle proof."""
+    _fields_ = [("z", ctypes.c_void_p), ("positions", ctypes.c_void_p), ("n_positions", ctypes.c_uint64),
+                ("nonce", ctypes.c_uint64)]
+
+
+class Overrides(ctypes.Structure):
+    """oracle_overrides (oracle/stark_oracle.c): caller-chosen challenges, each nullable."""
+    _fields_ = [("coeffs", ctypes.c_char_p), ("z", ctypes.c_char_p), ("deep_coeffs", ctypes.c_char_p),
+                ("alphas", ctypes.c_char_p), ("positions", ctypes.POINTER(ctypes.c_uint64)),
+                ("n_positions", ctypes.c_uint64)]
+
+
+def _prove_stages(air_id, trace_cols, width, n, pub, opts, ce, C, ov):
     L = lib()
+    head = [ctypes.c_int, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64,
+            ctypes.POINTER(ProofOptionsC)]
+    tail = [ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(Stages)]
     L.oracle_prove_stages.restype = ctypes.c_int
-    L.oracle_prove_stages.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint64,
-                                      ctypes.c_char_p, ctypes.c_uint64, ctypes.POINTER(ProofOptionsC),
-                                      ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)),
-                                      ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(Stages)]
+    L.oracle_prove_stages.argtypes = head + tail
+    L.oracle_prove_stages_with.restype = ctypes.c_int
+    L.oracle_prove_stages_with.argtypes = head + [ctypes.POINTER(Overrides)] + tail + [ctypes.POINTER(Queries)]
     bufs = {"coeffs": ctypes.create_string_buffer(16 * 1024), "comp_evals": ctypes.create_string_buffer(16 * n * ce),
             "ood": ctypes.create_string_buffer(16 * (2 * width + C)),
             "deep_coeffs": ctypes.create_string_buffer(16 * (width + C)),
-            "alphas": ctypes.create_string_buffer(16 * 16), "remainder": ctypes.create_string_buffer(16 * 256)}
+            "alphas": ctypes.create_string_buffer(16 * 16), "remainder": ctypes.create_string_buffer(16 * 256),
+            "z": ctypes.create_string_buffer(16), "positions": ctypes.create_string_buffer(8 * 255)}
     sd = Stages(*[ctypes.cast(bufs[k], ctypes.c_void_p) for k in
                   ("coeffs", "comp_evals", "ood", "deep_coeffs", "alphas", "remainder")], 0, 0, 0, 0)
+    qd = Queries(ctypes.cast(bufs["z"], ctypes.c_void_p), ctypes.cast(bufs["positions"], ctypes.c_void_p), 0, 0)
     out = ctypes.POINTER(ctypes.c_uint8)()
     olen = ctypes.c_uint64()
     oc = opts_c(opts)
-    rc = L.oracle_prove_stages(air_id, trace_cols, width, n, pub, len(pub) // 16, ctypes.byref(oc),
-                               ctypes.byref(out), ctypes.byref(olen), ctypes.byref(sd))
+    args = [air_id, trace_cols, width, n, pub, len(pub) // 16, ctypes.byref(oc)]
+    if ov is None:
+        name = "oracle_prove_stages"
+        rc = L.oracle_prove_stages(*args, ctypes.byref(out), ctypes.byref(olen), ctypes.byref(sd))
+    else:
+        name = "oracle_prove_stages_with"
+        rc = L.oracle_prove_stages_with(*args, ctypes.byref(ov), ctypes.byref(out), ctypes.byref(olen),
+                                        ctypes.byref(sd), ctypes.byref(qd))
     if rc != 0:
-        raise RuntimeError(f"oracle_prove_stages failed: {rc}")
+        raise RuntimeError(f"{name} failed: {rc}")
     proof = ctypes.string_at(out, olen.value)
     L.oracle_free(out)
     res = {"coeffs": bufs["coeffs"].raw[:16 * sd.n_coeffs], "comp_evals": bufs["comp_evals"].raw,
            "ood": bufs["ood"].raw, "deep_coeffs": bufs["deep_coeffs"].raw,
            "alphas": bufs["alphas"].raw[:16 * sd.n_layers], "remainder": bufs["remainder"].raw[:16 * sd.n_remainder]}
+    if ov is not None:
+        res.update({"z": int.from_bytes(bufs["z"].raw, "little"), "nonce": qd.nonce,
+                    "positions": [int(v) for v in np.frombuffer(bufs["positions"].raw, dtype="<u8")[:qd.n_positions]]})
     return proof, res
+
+
+def prove_stages(air_id: int, trace_cols: bytes, width: int, n: int, pub: bytes, opts, ce: int, C: int):
+    """Oracle proof + its stage values: dict of byte strings (16 B LE felts) keyed
+    coeffs, comp_evals (n*ce, natural CE order), ood (2w + C), deep_coeffs (w + C),
+    alphas (one per FRI layer), remainder."""
+    return _prove_stages(air_id, trace_cols, width, n, pub, opts, ce, C, None)
+
+
+def prove_stages_with(air_id: int, trace_cols: bytes, width: int, n: int, pub: bytes, opts, ce: int, C: int,
+                      coeffs=None, z=None, deep_coeffs=None, alphas=None, positions=None):
+    """prove_stages with caller-chosen challenges (oracle_prove_stages_with): coeffs,
+    deep_coeffs and alphas are lists of ints, z an int, positions a sorted list of
+    unique LDE positions; None leaves that site to the coin. With positions given the
+    oracle does not grind and writes nonce 0. The bytes have the proof's layout
+    (proof_format.sections) but verify only where nothing was overridden. The dict also
+    holds what the proof used at the remaining sites: z and nonce (ints), positions (list)."""
+    def pack(v):
+        return None if v is None else b"".join(fb(x) for x in v)
+    npos = 0 if positions is None else len(positions)
+    pos = None if positions is None else (ctypes.c_uint64 * npos)(*positions)
+    ov = Overrides(pack(coeffs), None if z is None else fb(z), pack(deep_coeffs), pack(alphas), pos, npos)
+    return _prove_stages(air_id, trace_cols, width, n, pub, opts, ce, C, ov)
 
 
 def mimc_hash_matrix(w, b, rc) -> int:

@@ -1,0 +1,366 @@
+"""Stage sessions and grinding driven with challenges the coin never draws.
+
+The stage entry points (include/zkp.h `zkp_session_*`, zkp_eval_constraints,
+zkp_ood_frame, zkp_deep_fri, zkp_query, zkp_grind) take every Fiat-Shamir value as an
+argument of the caller's channel. The other GPU tests pass the 128-bit pseudo-random
+values of DefaultRandomCoin<Blake3_256> for one seeded input; here the values are
+structured: coefficients of 0, 1, p - 1 and one-hot vectors, an OOD point inside the
+trace domain, FRI alphas of 0 and 1, the first and last LDE position, sibling leaves,
+the F positions of one FRI row, 255 adjacent positions, and further position sets on
+the same session.
+
+Reference: the CPU oracle under the same overrides (oracle_prove_stages_with). It works
+in coefficient form (Horner for the OOD frame, synthetic division for DEEP, an
+interpolation per folded row), so its value is defined wherever the device's pointwise
+form is. Every comparison is of field elements and digests: exact, no tolerance. Shapes
+and challenge tables: challenge_cases.py.
+
+Grinding: zkp_grind over seeds whose minimum nonce lies inside k_grind_all's first
+grid-stride pass, past it and past two passes, and proofs whose nonce lies past
+k_grind's first chunk (host tail, two-rank group) and past k_grind_all's first pass
+(device query tail); the expected nonces are the oracle's (test_challenge_cases.py)."""
+import contextlib
+import functools
+import threading
+
+import pytest
+
+import oracle_ref as O
+from air_strided_cases import mimc_strided_program
+from challenge_cases import (GRIND_CHUNK, GRIND_NONCES, GRIND_PROOFS, GU_DEVICES, SHAPES, TU_BATCH, alpha_cases,
+                             coeff_cases, combined_case, coset_points, deep_cases, grind_proof_options, grind_seed,
+                             layers, lde_size, position_cases, requery_sets, shape_options, z_cases, z_trace_rows)
+from proof_format import Reader, sections
+from test_gpu_options import gu_inputs, mimc_inputs, tu_inputs
+from zk_stark_project_amd import AIR_MIMC, MimcProver, _native
+from zk_stark_project_amd._native import ZkpError, verify_status
+from zk_stark_project_amd.field import P, to_bytes
+
+pytestmark = pytest.mark.gpu
+
+ZKP_ERR_ARGUMENT = 9
+
+
+def felts(b: bytes):
+    return [int.from_bytes(b[i:i + 16], "little") for i in range(0, len(b), 16)]
+
+
+@functools.lru_cache(maxsize=None)
+def shape_inputs(name):
+    """-> (the oracle's AIR id, trace, public elements, options, Shape)."""
+    sp = SHAPES[name]
+    if sp.kind == "global_update":
+        inputs = gu_inputs(GU_DEVICES, sp.n)
+    elif sp.kind == "training_update":
+        inputs = tu_inputs(TU_BATCH)
+    else:
+        inputs = mimc_inputs(sp.n)
+    air, trace, pub_el = inputs
+    assert trace.data.shape[:2] == (sp.w, sp.n)
+    return air, trace, pub_el, shape_options(sp), sp
+
+
+@contextlib.contextmanager
+def session_air(name):
+    """The AIR id the session is created with: the built-in one, or MiMC registered as a program."""
+    air, _, pub_el, _, sp = shape_inputs(name)
+    if sp.kind == "program":
+        with mimc_strided_program(sp.n, pub_el, "periodic").register() as prog:
+            yield prog
+    else:
+        yield air
+
+
+def reference(name, **ov):
+    air, trace, pub_el, opts, sp = shape_inputs(name)
+    ref, st = O.prove_stages_with(air, trace.to_bytes(), sp.w, sp.n, to_bytes(pub_el), opts, sp.ce, sp.C, **ov)
+    for key in ("coeffs", "deep_coeffs", "alphas"):  # the oracle used the values it was given
+        assert key not in ov or felts(st[key]) == ov[key]
+    assert "z" not in ov or st["z"] == ov["z"]
+    assert "positions" not in ov or st["positions"] == ov["positions"]
+    return st, sections(ref)
+
+
+def opened_values(blob, groups):
+    """The values of `groups` consecutive (values, batch paths) pairs, each a list of felts."""
+    r = Reader(blob)
+    out = []
+    for _ in range(groups):
+        out.append(felts(r.take(r.uint(4))))
+        r.take(r.uint(4))
+    return out
+
+
+def run_session(ctx, name, ov, more_queries=(), before=None):
+    """One session driven with the overrides `ov` (every other challenge is the one the
+    oracle's coin drew under them): trace root, constraint evaluations, constraint root,
+    OOD frame, every FRI layer root the channel callback sees, remainder, remainder
+    commitment and the openings against the oracle. more_queries: further position sets
+    asked of the same session, each against an oracle run with those positions.
+    before: {stage name: callable(session)} run ahead of that stage (the refusals).
+    -> what the session returned, the oracle's stage values and proof sections."""
+    _, trace, pub_el, opts, sp = shape_inputs(name)
+    st, sec = reference(name, **ov)
+    com = sec["commitments"]
+    L = layers(sp)
+    before = before or {}
+    got = {}
+    with session_air(name) as air:
+        s = _native.Session(ctx, air, sp.w, sp.n, list(pub_el), opts)
+        try:
+            assert s.fri_layers == L == len(st["alphas"]) // 16
+            assert s.trace_lde(trace.data) == com[0:32], "trace root"
+            before.get("eval", lambda s: None)(s)
+            got["evals"] = s.eval_constraints(felts(st["coeffs"]))
+            assert got["evals"].tobytes() == st["comp_evals"], "constraint evaluations (natural CE order)"
+            assert s.composition_commit() == com[32:64], "constraint root"
+            assert s.num_columns == sp.C
+            before.get("ood", lambda s: None)(s)
+            got["trace_ood"], got["comp_ood"] = s.ood_frame(st["z"])
+            assert to_bytes(got["trace_ood"] + got["comp_ood"]) == st["ood"], "OOD frame"
+            assert to_bytes(got["trace_ood"]) == sec["ood_trace"] and to_bytes(got["comp_ood"]) == sec["ood_comp"]
+            before.get("deep", lambda s: None)(s)
+            alphas = felts(st["alphas"])
+            seen = []
+
+            def channel(layer, root):
+                assert root == com[64 + 32 * layer: 96 + 32 * layer], f"FRI layer {layer} root"
+                seen.append(layer)
+                return alphas[layer]
+            got["remainder"], rcommit = s.deep_fri(felts(st["deep_coeffs"]), channel)
+            assert seen == list(range(L))
+            assert to_bytes(got["remainder"]) == st["remainder"] == sec["remainder"], "remainder"
+            assert rcommit == com[-32:], "remainder commitment"
+            before.get("query", lambda s: None)(s)
+            got["openings"] = s.query(st["positions"])
+            assert got["openings"] == sec["queries"] + sec["fri_queries"], "openings"
+            got["more"] = []
+            for pos in more_queries:
+                st2, sec2 = reference(name, **{**ov, "positions": pos})
+                assert sec2["commitments"] == com and st2["remainder"] == st["remainder"]
+                got["more"].append(s.query(pos))
+                assert got["more"][-1] == sec2["queries"] + sec2["fri_queries"], f"openings at {pos[:4]}.."
+        finally:
+            s.close()
+    return got, st, sec
+
+
+def case_ids(builder):
+    return [(name, case) for name in SHAPES for case in builder(SHAPES[name])]
+
+
+# ---------------------------------------------------------------- composition coefficients
+@pytest.mark.parametrize("name,case", case_ids(coeff_cases))
+def test_composition_coefficients(ctx, name, case):
+    """All 0 / 1 / p - 1 and one-hot at the first and last transition and assertion
+    coefficient. All 0: the evaluations, every opened composition value and the
+    composition OOD are zero (the derived-last-column check of composition_commit runs
+    on an all-zero composition)."""
+    sp = SHAPES[name]
+    got, st, sec = run_session(ctx, name, {"coeffs": coeff_cases(sp)[case]})
+    if case == "zero":
+        assert not got["evals"].any()
+        assert got["comp_ood"] == [0] * sp.C
+        comp_values = opened_values(sec["queries"][1:], 2)[1]
+        assert len(comp_values) == sp.C * len(st["positions"]) and not any(comp_values)
+
+
+# ---------------------------------------------------------------- OOD point
+@pytest.mark.parametrize("name,case", case_ids(z_cases))
+def test_ood_point(ctx, name, case):
+    """z = 0, 2, p - 2, and z = w_n^k inside the trace domain (k = 0, 1, n / 2, n - 1: at
+    the last, z * w_n wraps to 1): there, whatever the oracle says, the frame is trace
+    row k and row (k + 1) mod n."""
+    _, trace, _, _, sp = shape_inputs(name)
+    got, _, _ = run_session(ctx, name, {"z": z_cases(sp)[case]})
+    if case in z_trace_rows(sp):
+        k = z_trace_rows(sp)[case]
+        row = lambda t: [int(trace.data[c, t, 0]) | (int(trace.data[c, t, 1]) << 64) for c in range(sp.w)]
+        assert got["trace_ood"][:sp.w] == row(k)
+        assert got["trace_ood"][sp.w:] == row((k + 1) % sp.n)
+
+
+# ---------------------------------------------------------------- DEEP coefficients
+@pytest.mark.parametrize("name,case", case_ids(deep_cases))
+def test_deep_coefficients(ctx, name, case):
+    """All 0 / p - 1 and one-hot on the first and last trace column and the last
+    composition column. All 0: every FRI layer and the remainder are zero, and the
+    roots of those all-zero layers are the oracle's."""
+    sp = SHAPES[name]
+    got, st, sec = run_session(ctx, name, {"deep_coeffs": deep_cases(sp)[case]})
+    if case == "zero":
+        assert got["remainder"] == [0] * len(got["remainder"])
+        for values in opened_values(sec["fri_queries"][1:], layers(sp)):
+            assert values and not any(values)
+
+
+# ---------------------------------------------------------------- FRI alphas
+@pytest.mark.parametrize("name,case", case_ids(alpha_cases))
+def test_fri_alphas(ctx, name, case):
+    """Every alpha 0 / 1 / p - 1, a distinct small value per layer, 0 on the last layer only."""
+    sp = SHAPES[name]
+    run_session(ctx, name, {"alphas": alpha_cases(sp)[case]})
+
+
+# ---------------------------------------------------------------- query positions
+@pytest.mark.parametrize("name,case", case_ids(position_cases))
+def test_query_positions(ctx, name, case):
+    """Position 0, N - 1, both, one sibling pair, the F positions of one first-layer FRI
+    row, 255 adjacent positions at either end and every second position, each the first
+    query of a fresh session (GlobalUpdate has filled no lazy row before it)."""
+    run_session(ctx, name, {"positions": position_cases(SHAPES[name])[case]})
+
+
+@pytest.mark.parametrize("name", ["mimc_f2", "mimc_f16", "global_update"])
+def test_requery_other_positions(ctx, name):
+    """zkp_query again on the same session with other positions (a re-grind): A, a
+    disjoint B, A again, each the oracle's; GlobalUpdate fills its lazily derived paired
+    columns for the rows of B after those of A."""
+    A, B = requery_sets(SHAPES[name])
+    got, _, _ = run_session(ctx, name, {"positions": A}, more_queries=[B, A])
+    assert got["more"][1] == got["openings"] and got["more"][0] != got["openings"]
+
+
+# ---------------------------------------------------------------- everything at once
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_every_site_overridden(ctx, name):
+    run_session(ctx, name, combined_case(SHAPES[name]))
+
+
+# ---------------------------------------------------------------- refusals
+def refused(call):
+    with pytest.raises(ZkpError) as e:
+        call()
+    assert e.value.code == ZKP_ERR_ARGUMENT
+
+
+@pytest.mark.parametrize("name", ["mimc_f2", "global_update"])
+def test_refusals(ctx, name):
+    """A value >= p as composition coefficient, z, DEEP coefficient or alpha, a z on the
+    LDE coset, and position lists that are empty, too long, unsorted, repeated or out of
+    range: ZKP_ERR_ARGUMENT each, the session stays at its stage, and run_session goes
+    on to compare every later stage and a valid query with the oracle."""
+    sp = SHAPES[name]
+    st, _ = reference(name)
+    N = lde_size(sp)
+    top = (1 << 128) - 1
+
+    def bad_coeffs(s):
+        for v in (P, top):
+            for i in (0, sp.num_t + sp.num_a - 1):
+                c = felts(st["coeffs"])
+                c[i] = v
+                refused(lambda: s.eval_constraints(c))
+
+    def bad_z(s):
+        for z in (P, top, *coset_points(sp)):
+            refused(lambda: s.ood_frame(z))
+
+    def bad_deep(s):
+        for v in (P, top):
+            for i in (0, sp.w + sp.C - 1):
+                g = felts(st["deep_coeffs"])
+                g[i] = v
+                refused(lambda: s.deep_fri(g, lambda layer, root: 1))
+        alphas = felts(st["alphas"])
+        for v in (P, top):  # the last layer's alpha: the layers before it were folded with valid ones
+            refused(lambda: s.deep_fri(felts(st["deep_coeffs"]),
+                                       lambda layer, root: v if layer == layers(sp) - 1 else alphas[layer]))
+
+    def bad_positions(s):
+        for pos in ([], list(range(256)), [9, 4], [4, 4], [0, N], [N]):
+            refused(lambda: s.query(pos))
+
+    run_session(ctx, name, {}, before={"eval": bad_coeffs, "ood": bad_z, "deep": bad_deep, "query": bad_positions},
+                more_queries=[position_cases(sp)["both_ends"]])
+
+
+@pytest.mark.parametrize("name", ["mimc_f16", "training_update"])
+def test_ood_point_on_the_lde_coset(ctx, name):
+    """z = 3 and z = 3 * w_N^5 are points of the LDE coset, where the DEEP quotient is
+    divided pointwise by (x - z)(x - z * w_n): zkp_ood_frame refuses them before a launch
+    (the kernel statistics stay as they were) and then takes a valid z."""
+    sp = SHAPES[name]
+
+    def bad_z(s):
+        ctx.set_profiling(True)
+        try:
+            ctx.reset_stats()
+            for z in coset_points(sp):
+                refused(lambda: s.ood_frame(z))
+            assert ctx.stats_table() == {}
+        finally:
+            ctx.set_profiling(False)
+            ctx.reset_stats()
+    run_session(ctx, name, {"z": z_cases(sp)["two"]}, before={"ood": bad_z})
+
+
+# ---------------------------------------------------------------- grinding
+@pytest.mark.parametrize("bits,i", [(bits, i) for bits in sorted(GRIND_NONCES) for i in range(8)])
+def test_grind_seed_sweep(ctx, bits, i):
+    """zkp_grind (k_grind_all) returns the minimum nonce, not just a valid one: minima
+    inside the first pass of 2^18 nonces, past it, and several passes on."""
+    assert ctx.grind(O.blake3(grind_seed(i)), bits) == GRIND_NONCES[bits][i]
+
+
+def grind_inputs(g):
+    opts = grind_proof_options(g)
+    p = MimcProver(opts)
+    trace = p.build_trace(g.start, g.n)
+    pub_el = tuple(p.get_pub_inputs(trace).to_elements())
+    ref, otr = O.prove(AIR_MIMC, trace.to_bytes(), 1, g.n, to_bytes(pub_el), opts)
+    assert otr.pow_nonce == g.nonce
+    return trace, pub_el, opts, ref
+
+
+@pytest.mark.parametrize("name", ["host_tail", "device_tail"])
+def test_proof_nonce_past_the_first_grinding_unit(ctx, name):
+    """host_tail: no device tail, so ProofRun::grind_stage launches k_grind once per chunk
+    of 2^22 nonces and the nonce lies in a later chunk than the first. device_tail: one
+    k_grind_all launch whose minimum lies past its first pass. Bytes == the oracle's."""
+    g = GRIND_PROOFS[name]
+    trace, pub_el, opts, ref = grind_inputs(g)
+    ctx.set_profiling(True)
+    try:
+        ctx.reset_stats()
+        gpu, tr = ctx.prove(AIR_MIMC, trace.data, pub_el, opts)
+        launches = ctx.stats_table()["grind"]["launches"]
+    finally:
+        ctx.set_profiling(False)
+        ctx.reset_stats()
+    assert tr.pow_nonce == g.nonce
+    assert gpu == ref
+    assert verify_status(AIR_MIMC, gpu, pub_el, opts) == 0
+    assert launches == ((g.nonce - 1) // GRIND_CHUNK + 1 if name == "host_tail" else 1)
+
+
+def test_proof_nonce_past_the_first_chunk_two_ranks(ctx):
+    """An in-process group of two: the first chunk runs on the device coin behind the
+    remainder, the later ones from grind_stage on every rank. Both ranks return the oracle's bytes."""
+    g = GRIND_PROOFS["two_ranks"]
+    assert g.world == 2
+    trace, pub_el, opts, ref = grind_inputs(g)
+    comms = _native.local_group(2)
+    ctxs = [_native.Context(0) for _ in range(2)]
+    out = [None, None]
+
+    def run(r):
+        try:
+            out[r] = ctxs[r].prove_sharded(comms[r], AIR_MIMC, trace.data, pub_el, opts)
+        except Exception as e:  # noqa: BLE001 — reported by the assertions below
+            out[r] = e
+    try:
+        threads = [threading.Thread(target=run, args=(r,)) for r in range(2)]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        for res in out:
+            assert not isinstance(res, Exception), res
+            assert res[1].pow_nonce == g.nonce
+            assert res[0] == ref
+    finally:
+        for c in comms:
+            c.close()
+        for c in ctxs:
+            c.close()

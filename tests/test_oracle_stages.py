@@ -1,6 +1,8 @@
 """CPU: the oracle's stage dump (oracle_prove_stages, the checker of the stage
 entry points) is consistent with the oracle's own proof, and the proof section
 parser (tests/proof_format.py) round-trips oracle proofs of every AIR."""
+import pytest
+
 import oracle_ref as O
 from proof_format import sections
 from test_gpu_parity import mimc_case
@@ -34,3 +36,72 @@ def test_stage_dump_matches_proof_global_update():
     assert st["ood"] == sec["ood_trace"] + sec["ood_comp"]
     assert st["remainder"] == sec["remainder"]
     assert len(st["coeffs"]) == 16 * (60 + 120)
+
+
+def felts(b: bytes):
+    return [int.from_bytes(b[i:i + 16], "little") for i in range(0, len(b), 16)]
+
+
+def _own_draws(air_id, trace, w, n, pub, opts, ce, C):
+    """oracle_prove_stages_with fed the values the oracle drew itself."""
+    args = (air_id, trace.to_bytes(), w, n, pub, opts, ce, C)
+    proof, dump = O.prove_stages(*args)
+    plain, tr = O.prove(*args[:6])
+    assert proof == plain
+    again, st = O.prove_stages_with(*args)  # no override at all
+    assert again == proof and {k: st[k] for k in dump} == dump
+    assert st["z"] == tr.z.lo | (tr.z.hi << 64) and st["nonce"] == tr.pow_nonce
+    assert st["positions"] == list(tr.query_positions[:tr.num_unique_queries])
+    drawn = dict(coeffs=felts(st["coeffs"]), z=st["z"], deep_coeffs=felts(st["deep_coeffs"]),
+                 alphas=felts(st["alphas"]))
+    # each site alone and every challenge together: the same bytes
+    for ov in [{k: v} for k, v in drawn.items()] + [drawn]:
+        again, st2 = O.prove_stages_with(*args, **ov)
+        assert again == proof, sorted(ov)
+        assert st2 == st, sorted(ov)
+    # with the positions too nothing is ground: the same bytes but for a nonce of 0
+    again, st2 = O.prove_stages_with(*args, positions=st["positions"], **drawn)
+    assert sections(proof)["nonce"] == st["nonce"] > 0 and sections(again)["nonce"] == st2["nonce"] == 0
+    assert again[:-10] == proof[:-10] and again[-1:] == proof[-1:]  # u64 nonce, u8 0 at the end
+    assert {**st2, "nonce": st["nonce"]} == st
+    return proof, st
+
+
+def test_overrides_with_own_draws_mimc():
+    opts = ProofOptions(40, 8, 4, 1, 4, 0)  # three FRI layers
+    p, trace = mimc_case(64, opts)
+    pub = to_bytes(p.get_pub_inputs(trace).to_elements())
+    _, st = _own_draws(AIR_MIMC, trace, 1, 64, pub, opts, 8, 6)
+    assert len(st["alphas"]) == 16 * 3
+
+
+def test_overrides_with_own_draws_global_update():
+    opts = ProofOptions(40, 16, 4)
+    p = gu(6, 64, 1, opts)
+    trace = p.build_trace()
+    _own_draws(AIR_GLOBAL_UPDATE, trace, 120, 64, to_bytes(p.get_pub_inputs(trace).to_elements()), opts, 2, 1)
+
+
+def test_overrides_change_only_what_follows():
+    """One overridden site leaves every earlier commitment an ordinary proof's, and the
+    chosen value is the one in the stage dump; a position list is refused unless it is
+    sorted, unique, in range and of 1..255 entries."""
+    opts = ProofOptions(40, 8, 4, 1, 4, 0)
+    p, trace = mimc_case(64, opts)
+    pub = to_bytes(p.get_pub_inputs(trace).to_elements())
+    args = (AIR_MIMC, trace.to_bytes(), 1, 64, pub, opts, 8, 6)
+    proof, st = O.prove_stages(*args)
+    com = sections(proof)["commitments"]
+    other, st2 = O.prove_stages_with(*args, z=2)
+    c2 = sections(other)["commitments"]
+    assert st2["z"] == 2 and c2[:64] == com[:64] and c2[64:] != com[64:]
+    assert st2["coeffs"] == st["coeffs"] and st2["ood"] != st["ood"]
+    other, st2 = O.prove_stages_with(*args, alphas=[0, 1, 5])
+    c2 = sections(other)["commitments"]
+    assert felts(st2["alphas"]) == [0, 1, 5] and c2[:96] == com[:96] and c2[96:] != com[96:]
+    other, st2 = O.prove_stages_with(*args, positions=[0, 511])
+    assert st2["positions"] == [0, 511] and sections(other)["num_queries"] == 2
+    assert sections(other)["commitments"] == com
+    for bad in ([], list(range(256)), [3, 2], [2, 2], [512]):
+        with pytest.raises(RuntimeError):
+            O.prove_stages_with(*args, positions=bad)

@@ -196,6 +196,8 @@ int zkp_eval_constraints(zkp_session* s, const zkp_felt* coeffs, uint32_t n_coef
     s->begin(1);
     ProofRun& r = *s->run;
     if (n_coeffs != r.ncoef) return (int)ZKP_ERR_ARGUMENT;
+    for (uint32_t i = 0; i < n_coeffs; i++)
+      if (ge_p(make(coeffs[i].lo, coeffs[i].hi))) throw ZkpFail{ZKP_ERR_ARGUMENT, "non-canonical composition coefficient"};
     s->ctx->upload(r.dt_cc, coeffs, (size_t)n_coeffs * 16);
     r.eval_stage();
     if (evals_out) {  // CE-coset-major on the device -> natural CE domain order
@@ -252,8 +254,13 @@ int zkp_ood_frame(zkp_session* s, zkp_felt zf, zkp_felt* trace_ood, zkp_felt* co
     if (!trace_ood || !comp_ood) return (int)ZKP_ERR_ARGUMENT;
     s->begin(3);
     ProofRun& r = *s->run;
-    s->z = make(zf.lo, zf.hi);
-    if (ge_p(s->z)) return (int)ZKP_ERR_ARGUMENT;
+    const felt z = make(zf.lo, zf.hi);
+    if (ge_p(z)) throw ZkpFail{ZKP_ERR_ARGUMENT, "non-canonical OOD point"};
+    // z or z * w_n on the LDE coset 3 * <w_N>: the DEEP stage divides by (x - z)(x - z w_n)
+    // at every x of that coset. w_n^N = 1, so both have the N-th power of z
+    if (eq(pow_u64(z, s->N), pow_u64(felt_u64(3), s->N)))
+      throw ZkpFail{ZKP_ERR_ARGUMENT, "OOD point on the LDE domain"};
+    s->z = z;
     s->zg = mul(s->z, root_of_unity(s->logn));
     std::vector<felt> pw(2 * (size_t)s->logn), zz = {s->z, s->zg};
     felt a = s->z, b = s->zg;
@@ -287,7 +294,10 @@ int zkp_deep_fri(zkp_session* s, const zkp_felt* deep_coeffs, zkp_fri_channel ch
     const felt g = felt_u64(3);
     // DEEP coefficients and the OOD combinations kz = sum gamma_i T_i(z) (+ composition), kzg
     std::vector<felt> gam(w + C), dkh(4);
-    for (uint32_t i = 0; i < w + C; i++) gam[i] = make(deep_coeffs[i].lo, deep_coeffs[i].hi);
+    for (uint32_t i = 0; i < w + C; i++) {
+      gam[i] = make(deep_coeffs[i].lo, deep_coeffs[i].hi);
+      if (ge_p(gam[i])) throw ZkpFail{ZKP_ERR_ARGUMENT, "non-canonical DEEP coefficient"};
+    }
     felt kz = zero(), kzg = zero();
     for (uint32_t c = 0; c < w; c++) {
       kz = add(kz, mul(gam[c], s->ood[2 * c]));
