@@ -97,7 +97,12 @@ struct zkp_ctx {
       // which mid-proof would drain the queued work of this and every other stream
       // (a new shape's first proof grows dozens of buffers); free_retired() releases
       // them once the proof's streams are idle
-      if (b.p) retired.push_back(b.p);
+      // the new buffer is uninitialised: a table cached under this name is filled again
+      // (a key must fix its table's size; this keeps one that does not from reading garbage)
+      if (b.p) {
+        retired.push_back(b.p);
+        cached.erase(name);
+      }
       b.p = nullptr;
       HIP_CHECK(hipMalloc(&b.p, bytes));
       b.bytes = bytes;

@@ -253,8 +253,8 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
         const uint32_t gi = pa.ngroups++;
         const std::string key = "binv_prog_" + dom + "_" + std::to_string(air.a_step[k]);
         pa.w_step[gi] = pow_u64(wn, air.a_step[k]);
-        pa.dinv_ready[gi] = ctx->have_cached(key);
         pa.dinv[gi] = ctx->buf<felt>(key, (uint64_t)cel * n);
+        pa.dinv_ready[gi] = ctx->have_cached(key);
       }
       pa.grp_end[pa.ngroups - 1] = (uint32_t)k + 1;
     }
@@ -328,9 +328,9 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
   if (!cel && !coef_form) return;
   // linear AIRs: the divisor tables and the final per-point formula (both forms)
   auto linear = [&](LinearEvalArgs& la, const std::string& key) {
-    la.binv_ready = ctx->have_cached(key);
     la.binv = ctx->buf<felt>("binv_scratch", ((uint64_t)cel * n) / 2048 + 1);
     la.dinv = ctx->buf<felt>(key, (uint64_t)cel * n);
+    la.binv_ready = ctx->have_cached(key);
     if (!coef_form) {
       launch_eval_linear(pf, st, ec, la, tlde, comp);
       return;
@@ -369,9 +369,9 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
     ma.kper = dk;
     // divisor inverses depend only on the domain and the assertion steps: cache per config
     std::string key = "binv_mimc_" + dom;
-    ma.binv_ready = ctx->have_cached(key);
     ma.binv = ctx->buf<felt>("binv_scratch", ((uint64_t)cel * n) / 2048 + 1);
     ma.dinv = ctx->buf<felt>(key, (uint64_t)cel * n);
+    ma.binv_ready = ctx->have_cached(key);
     launch_eval_mimc(pf, st, ec, ma, tlde, comp);
   } else if (air.id == ZKP_AIR_GLOBAL_UPDATE) {
     // GlobalUpdate: T = sum_i a^i (k*next_i - k*cur_i - next_{i+60}); B = sum_c b_c (cur_c - v_c)
@@ -451,8 +451,11 @@ void deep_evaluations(zkp_ctx* ctx, zkp_comm* cm, hipStream_t st, DeepArgs da, c
   felt* alde = ctx->buf<felt>("deep_alde", (size_t)Bl * n);
   NttBatch lb{acomb, alde, Sj0, n, n, Bl, Bl, Bl};
   launch_ntt(ctx->prof, st, lb, da.logn, true, ctx->tws(logN), logN);
-  felt* g1 = ctx->buf<felt>("deep_g1", (size_t)da.C + 1);  // [1 | delta_0 .. delta_{C-1}]
-  if (!ctx->have_cached("deep_g1")) {
+  // [1 | delta_0 .. delta_{C-1}]; keyed by C: one name for every C regrew the buffer at a
+  // larger C and left its leading 1 unwritten
+  const std::string g1key = "deep_g1_" + std::to_string(da.C);
+  felt* g1 = ctx->buf<felt>(g1key, (size_t)da.C + 1);
+  if (!ctx->have_cached(g1key)) {
     const felt unit = one();
     ctx->upload(g1, &unit, 16);
   }
