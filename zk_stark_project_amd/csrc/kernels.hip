@@ -198,46 +198,25 @@ __device__ __forceinline__ void block_batch_inverse(felt* v, felt* s_pre, felt* 
   });
 }
 
+// point_x for the split batch inversion, whose cosets may hold one point each (no w_n table)
+__device__ __forceinline__ felt den_point_x(const PointMap& m, uint64_t q) {
+  return m.logn ? point_x(m, q) : m.cx[q];
+}
+
 // Phase 1 of the split batch inversion: product of the denominators
 // (x_q - c0)(x_q - c1) (or (x_q - c0) when !two) of each block's EVAL_CH*TPB
-// local points q (EVAL_POINT), x_q = point_x(m, q). Same point->block mapping
+// local points q (EVAL_POINT), x_q = den_point_x(m, q). Same point->block mapping
 // as the phase-3 kernels.
-// With pw (DEEP: pw[l] = c0^(2^l), pw[logn + l] = c1^(2^l)), block 0 also writes
-// the inverse of the product over ALL points to *tinv, from the closed form
-// prod_t (cx_j w_n^t - c) = c^n - cx_j^n per coset (n even): prod_j (c0^n -
-// cx_j^n)(c1^n - cx_j^n). Its field inversion then runs beside the other
-// blocks instead of after them in k_invert_products.
+// With csq the point is on the device: c0 = (*csq)^2 (DEEP: z^8 from z^4).
 __global__ __launch_bounds__(TPB) void k_den_products(PointMap m, uint64_t count, felt c0, felt c1, int two,
-                                                      const felt* __restrict__ cdev, const felt* __restrict__ pw,
-                                                      felt* __restrict__ tinv, felt* __restrict__ prod) {
+                                                      const felt* __restrict__ csq, felt* __restrict__ prod) {
   __shared__ felt s[TPB];
-  if (cdev) {  // points drawn on the device (DEEP: z, z*w_n)
-    c0 = cdev[0];
-    c1 = cdev[1];
-  }
-  if (pw && blockIdx.x == 0) {
-    const uint32_t ncos = (uint32_t)(count >> m.logn);
-    const felt zn = sqr(pw[m.logn - 1]), zgn = sqr(pw[2 * m.logn - 1]);
-    felt acc = one();
-    for (uint32_t j = threadIdx.x; j < ncos; j += TPB) {
-      felt cn = m.cx[j];
-      for (uint32_t l = 0; l < m.logn; l++) cn = sqr(cn);
-      acc = mul(acc, mul(sub(zn, cn), sub(zgn, cn)));
-    }
-    s[threadIdx.x] = acc;
-    __syncthreads();
-    for (uint32_t h = TPB / 2; h >= 1; h >>= 1) {
-      if (threadIdx.x < h) s[threadIdx.x] = mul(s[threadIdx.x], s[threadIdx.x + h]);
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) *tinv = inv(s[0]);
-    __syncthreads();
-  }
+  if (csq) c0 = sqr(csq[0]);
   felt acc = one();
   static_for<0, EVAL_CH>([&](auto k) {
     const uint64_t q = EVAL_POINT(k);
     if (q < count) {
-      felt x = point_x(m, q);
+      felt x = den_point_x(m, q);
       felt d = sub(x, c0);
       if (two) d = mul(d, sub(x, c1));
       acc = mul(acc, d);
@@ -252,9 +231,11 @@ __global__ __launch_bounds__(TPB) void k_den_products(PointMap m, uint64_t count
   if (threadIdx.x == 0) prod[blockIdx.x] = s[0];
 }
 
-// Phase 2: invert all block products in place with one field inversion (or
-// none: tinv = the inverse of their product, precomputed by k_den_products).
-__global__ __launch_bounds__(1024) void k_invert_products(felt* prod, uint32_t nb, const felt* __restrict__ tinv) {
+// Phase 2: invert all block products in place with one field inversion. With
+// `cof` there is none: prod[b] becomes the product of all the other blocks'
+// products, T / prod[b] for the product T over all points, and the phase-3 tables
+// come out scaled by T (DEEP: k_deep_total_inv inverts T meanwhile).
+__global__ __launch_bounds__(1024) void k_invert_products(felt* prod, uint32_t nb, int cof) {
   __shared__ felt s_pre[1024], s_suf[1024];
   __shared__ felt s_inv;
   const uint32_t t = threadIdx.x;
@@ -275,7 +256,7 @@ __global__ __launch_bounds__(1024) void k_invert_products(felt* prod, uint32_t n
     s_suf[t] = mul(s_suf[t], b);
     __syncthreads();
   }
-  if (t == 0) s_inv = tinv ? *tinv : inv(s_pre[1023]);
+  if (t == 0) s_inv = cof ? one() : inv(s_pre[1023]);
   __syncthreads();
   felt ia = s_inv;
   if (t > 0) ia = mul(ia, s_pre[t - 1]);
@@ -296,14 +277,16 @@ __global__ __launch_bounds__(1024) void k_invert_products(felt* prod, uint32_t n
 // (cached per domain in the ctx, so constraint evaluation reads one felt per
 // point instead of redoing the batch inversion every proof).
 __global__ __launch_bounds__(TPB) void k_den_table(PointMap m, uint64_t count, felt c0, felt c1, int two,
-                                                   const felt* __restrict__ binv, felt* __restrict__ out) {
+                                                   const felt* __restrict__ csq, const felt* __restrict__ binv,
+                                                   felt* __restrict__ out) {
   __shared__ felt s_pre[TPB], s_suf[TPB];
+  if (csq) c0 = sqr(csq[0]);  // as k_den_products
   felt den[EVAL_CH];
   static_for<0, EVAL_CH>([&](auto k) {
     const uint64_t q = EVAL_POINT(k);
     den[k] = one();
     if (q < count) {
-      felt x = point_x(m, q);
+      felt x = den_point_x(m, q);
       felt d = sub(x, c0);
       if (two) d = mul(d, sub(x, c1));
       den[k] = d;
@@ -314,6 +297,64 @@ __global__ __launch_bounds__(TPB) void k_den_table(PointMap m, uint64_t count, f
     const uint64_t q = EVAL_POINT(k);
     if (q < count) out[q] = den[k];
   });
+}
+
+// 1 / T for T = the product of (y - c0), c0 = (*csq)^2, over the ncos whole cosets
+// of m, from the closed form prod_t (cx_j w_n^t - c0) = c0^n - cx_j^n per coset
+// (n even; cx_j - c0 when n = 1). One block: the one field inversion of the DEEP
+// denominators, on a stream of its own beside the scaled table's three phases.
+__global__ __launch_bounds__(TPB) void k_deep_total_inv(PointMap m, uint32_t ncos, const felt* __restrict__ csq,
+                                                        felt* __restrict__ tinv) {
+  __shared__ felt s[TPB];
+  felt zn = sqr(csq[0]);
+  for (uint32_t l = 0; l < m.logn; l++) zn = sqr(zn);
+  felt acc = one();
+  for (uint32_t j = threadIdx.x; j < ncos; j += TPB) {
+    felt cn = m.cx[j];
+    for (uint32_t l = 0; l < m.logn; l++) cn = sqr(cn);
+    acc = mul(acc, m.logn ? sub(zn, cn) : sub(cn, zn));
+  }
+  s[threadIdx.x] = acc;
+  __syncthreads();
+  for (uint32_t h = TPB / 2; h >= 1; h >>= 1) {
+    if (threadIdx.x < h) s[threadIdx.x] = mul(s[threadIdx.x], s[threadIdx.x + h]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *tinv = inv(s[0]);
+}
+
+// DEEP inverse table, out[q] = 1 / (x_q - z) over whole cosets (q = j*n + t,
+// x_q = cx[j] w_n^t), expanded from the table over the 8th powers. The points
+// x0 w_8^i, i < 8, are rows t0 + i*n/8 of one coset, and prod_i (x0 w_8^i - z) =
+// z^8 - x0^8: thread e = j*n/8 + t0 seeds Montgomery's trick over those 8 with
+// -small[e] / T, small[e] = T / (x0^8 - z^8), *tinv = 1 / T. 4 products for the
+// points (w_8^4 = -1), 6 prefix and 14 back-substitution products, no LDS; lanes
+// are consecutive t0.
+__global__ __launch_bounds__(TPB) void k_deep_inv_expand(PointMap m, uint64_t count, const felt* __restrict__ zz,
+                                                         DeepRoots r, const felt* __restrict__ small,
+                                                         const felt* __restrict__ tinv, felt* __restrict__ out) {
+  const uint64_t e = blockIdx.x * (uint64_t)TPB + threadIdx.x;
+  if (e >= count >> 3) return;
+  const uint32_t lg = m.logn - 3;
+  const uint64_t j = e >> lg, t0 = e & ((1ull << lg) - 1);
+  const felt z = zz[0];
+  felt d[8], pre[7];
+  d[0] = mul(m.cx[j], m.twn[t0]);  // t0 < n/8: in the table's half
+  d[1] = mul(d[0], r.w8);
+  d[2] = mul(d[0], r.w8_2);
+  d[3] = mul(d[0], r.w8_3);
+  static_for<0, 4>([&](auto i) { d[4 + i] = neg(d[i]); });
+  static_for<0, 8>([&](auto i) { d[i] = sub(d[i], z); });
+  pre[0] = d[0];
+  static_for<1, 7>([&](auto i) { pre[i] = mul(pre[i - 1], d[i]); });
+  felt ia = neg(mul(small[e], tinv[0]));
+  felt* o = out + (j << m.logn) + t0;
+  static_for<0, 7>([&](auto ii) {
+    constexpr int i = 7 - decltype(ii)::value;
+    o[(uint64_t)i << lg] = mul(ia, pre[i - 1]);
+    ia = mul(ia, d[i]);
+  });
+  o[0] = ia;
 }
 
 // CE point of local index q (CE-coset-major over the shard's CE cosets):
@@ -983,9 +1024,12 @@ __global__ __launch_bounds__(TPB) void k_eval_bitrev_tail(const felt* __restrict
 
 // local point q = jl*n + t of the shard's cosets: LDE index i = (j0 + jl) + B*t;
 // the LDE matrices are read at offset q (contiguous), output is coset-major.
-__global__ __launch_bounds__(TPB) void k_deep(DeepArgs a, const felt* __restrict__ binv, felt* __restrict__ out) {
-  __shared__ felt s_pre[TPB], s_suf[TPB];
-  const felt z = a.dk[0], zg = a.dk[1], kz = a.dk[2], kzg = a.dk[3];
+// inv[q] = 1 / (x_q - z) (k_deep_inv_expand). x_t = c_j w_n^t within a coset, so
+// 1 / (x_t - z w_n) = w_n^-1 / (x_{t-1} - z): the second denominator is the
+// coset's previous table entry (cyclic) times ginv = w_n^-1.
+__global__ __launch_bounds__(TPB) void k_deep(DeepArgs a, const felt* __restrict__ inv, felt* __restrict__ out) {
+  const felt kz = a.dk[2], kzg = a.dk[3];
+  const uint64_t n = 1ull << a.logn;
   const uint64_t N = 1ull << (a.logn + a.logBl);
   const uint64_t cstride = N;
   felt A[EVAL_CH], Bh[EVAL_CH];
@@ -1012,18 +1056,16 @@ __global__ __launch_bounds__(TPB) void k_deep(DeepArgs a, const felt* __restrict
     static_for<0, EVAL_CH>([&](auto k) { v[k] = col[off[k]]; });
     static_for<0, EVAL_CH>([&](auto k) { Bh[k] = add(Bh[k], mul(gh, v[k])); });
   }
-  felt num[EVAL_CH], den[EVAL_CH];
+  felt i0[EVAL_CH], i1[EVAL_CH];
   static_for<0, EVAL_CH>([&](auto k) {
-    const bool valid = EVAL_POINT(k) < N;
-    felt x = point_x(a.pm, off[k]);
-    felt e1 = sub(x, z), e2 = sub(x, zg);
-    num[k] = add(mul(sub(add(A[k], Bh[k]), kz), e2), mul(sub(A[k], kzg), e1));
-    den[k] = valid ? mul(e1, e2) : one();
+    i0[k] = inv[off[k]];
+    i1[k] = inv[(off[k] & (n - 1)) ? off[k] - 1 : off[k] + (n - 1)];
   });
-  block_batch_inverse(den, s_pre, s_suf, binv[blockIdx.x]);
   static_for<0, EVAL_CH>([&](auto k) {
     const uint64_t q = EVAL_POINT(k);
-    if (q < N) out[q] = mul(num[k], den[k]);
+    const felt t0 = mul(sub(add(A[k], Bh[k]), kz), i0[k]);
+    const felt t1 = mul(mul(sub(A[k], kzg), a.ginv), i1[k]);
+    if (q < N) out[q] = add(t0, t1);
   });
 }
 
@@ -1523,23 +1565,23 @@ void launch_build_coset_scale(Prof& prof, hipStream_t s, felt* S, uint32_t logn,
 }
 
 
-// prod: nb block products (+1 slot for the closed-form total inverse when pw is given)
+// prod: nb block products. With csq (c0 = (*csq)^2 on the device) no field inversion
+// runs here: the phase-3 tables come out scaled by the product over all points
 static void launch_den_inverse(Prof& prof, hipStream_t s, const PointMap& m, uint64_t count, felt c0, felt c1,
-                               int two, felt* prod, const felt* cdev = nullptr, const felt* pw = nullptr) {
+                               int two, felt* prod, const felt* csq = nullptr) {
   uint32_t nb = blocks_for((count + EVAL_CH - 1) / EVAL_CH);
-  felt* tinv = pw ? prod + nb : nullptr;
   LAUNCH(prof, "den_products", s, (double)count * 16.0,
-         hipLaunchKernelGGL(k_den_products, dim3(nb), dim3(TPB), 0, s, m, count, c0, c1, two, cdev, pw, tinv, prod));
+         hipLaunchKernelGGL(k_den_products, dim3(nb), dim3(TPB), 0, s, m, count, c0, c1, two, csq, prod));
   LAUNCH(prof, "invert_products", s, (double)nb * 32.0,
-         hipLaunchKernelGGL(k_invert_products, dim3(1), dim3(1024), 0, s, prod, nb, tinv));
+         hipLaunchKernelGGL(k_invert_products, dim3(1), dim3(1024), 0, s, prod, nb, csq ? 1 : 0));
 }
 
 static void launch_den_table(Prof& prof, hipStream_t s, const PointMap& m, uint64_t count, felt c0, felt c1,
-                             int two, felt* prod, felt* table) {
-  launch_den_inverse(prof, s, m, count, c0, c1, two, prod);
+                             int two, felt* prod, felt* table, const felt* csq = nullptr) {
+  launch_den_inverse(prof, s, m, count, c0, c1, two, prod, csq);
   LAUNCH(prof, "den_table", s, (double)count * 16.0,
          hipLaunchKernelGGL(k_den_table, dim3(blocks_for((count + EVAL_CH - 1) / EVAL_CH)), dim3(TPB), 0, s, m, count,
-                            c0, c1, two, prod, table));
+                            c0, c1, two, csq, prod, table));
 }
 
 #ifdef ZKP_COUNT_REDO
@@ -1706,11 +1748,24 @@ void launch_eval_bitrev(Prof& prof, hipStream_t s, const felt* arrays, uint32_t 
   launch_eval_bitrev_tail(prof, s, partial, narrays, logn, nb, pw0, pw1, ninv, out);
 }
 
-void launch_deep_denominators(Prof& prof, hipStream_t s, const PointMap& m, uint64_t count, const felt* zz,
-                              const felt* pw, felt* binv) {
-  if (count & ((1ull << m.logn) - 1))  // whole cosets only (closed-form total)
+void launch_deep_denominators(Prof& prof, hipStream_t s, hipStream_t s2, hipEvent_t ev, const PointMap& m,
+                              const PointMap& m8, const DeepRoots& r, uint64_t count, const felt* zz, const felt* pw,
+                              felt* scratch, felt* table) {
+  // whole cosets only (closed-form total, groups of 8 rows n/8 apart)
+  if (m.logn < 3 || m8.logn + 3 != m.logn || (count & ((1ull << m.logn) - 1)))
     launch_fail(ZKP_ERR_DEVICE, "internal: DEEP denominators over a partial coset");
-  launch_den_inverse(prof, s, m, count, zero(), zero(), 1, binv, zz, pw);
+  // T / (y - z^8) over the count/8 eighth powers y, z^8 = pw[2]^2, T = their product over
+  // all y: three phases without an inversion, while s2 inverts T; then 8 inverses from each
+  const uint64_t c8 = count >> 3;
+  felt* tinv = scratch + deep_den_scratch(count) - 1;
+  LAUNCH(prof, "deep_total_inv", s2, 0.0,
+         hipLaunchKernelGGL(k_deep_total_inv, dim3(1), dim3(TPB), 0, s2, m8, (uint32_t)(c8 >> m8.logn), pw + 2, tinv));
+  if (hipEventRecord(ev, s2) != hipSuccess) launch_fail(ZKP_ERR_DEVICE, "DEEP denominators: event record");
+  launch_den_table(prof, s, m8, c8, zero(), zero(), 0, scratch + c8, scratch, pw + 2);
+  if (hipStreamWaitEvent(s, ev, 0) != hipSuccess) launch_fail(ZKP_ERR_DEVICE, "DEEP denominators: event wait");
+  LAUNCH(prof, "deep_inv_expand", s, (double)count * 18.0,
+         hipLaunchKernelGGL(k_deep_inv_expand, dim3(blocks_for(c8)), dim3(TPB), 0, s, m, count, zz, r, scratch, tinv,
+                            table));
 }
 
 void launch_deep_lincomb(Prof& prof, hipStream_t s, const felt* coef, uint32_t w, uint64_t n, uint64_t p0,
@@ -1730,8 +1785,8 @@ void launch_deep_lincomb(Prof& prof, hipStream_t s, const felt* coef, uint32_t w
 
 void launch_deep(Prof& prof, hipStream_t s, const DeepArgs& a, felt* out) {
   uint64_t N = 1ull << (a.logn + a.logBl);
-  LAUNCH(prof, "deep", s, (double)N * ((a.w + a.C) * 16.0 + 16.0),
-         hipLaunchKernelGGL(k_deep, dim3(blocks_for((N + EVAL_CH - 1) / EVAL_CH)), dim3(TPB), 0, s, a, a.binv, out));
+  LAUNCH(prof, "deep", s, (double)N * ((a.w + a.C) * 16.0 + 32.0),
+         hipLaunchKernelGGL(k_deep, dim3(blocks_for((N + EVAL_CH - 1) / EVAL_CH)), dim3(TPB), 0, s, a, a.inv, out));
 }
 
 void launch_comp_dft(Prof& prof, hipStream_t s, const felt* recv, const uint32_t* blk, const felt* Si,

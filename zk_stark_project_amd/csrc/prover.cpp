@@ -375,13 +375,23 @@ void ProofRun::composition_stage() {
 // 5a. OOD frame at z = dt_zz[0] (powers in dt_pw; sharded: every rank holds all
 // coefficients and sums 1/R of each array's blocks) and the DEEP denominators
 void ProofRun::ood_values() {
-  // the DEEP denominators (x - z)(x - zg) only need z: their batch-inversion
-  // phases run on the side stream beside the OOD evaluation and its transcript
-  deep_binv = ctx->buf<felt>("binv", ((uint64_t)Bl * n) / 2048 + 1);
-  deep_pm = PointMap{cx + j0, twn, logn};
+  // the DEEP denominators 1 / (x - z) only need z (1 / (x - zg) is the previous row's
+  // times w_n^-1): their table is built on the side stream beside the OOD evaluation
+  // and its transcript
+  const uint64_t cnt = (uint64_t)Bl * n;
+  deep_inv = ctx->buf<felt>("deep_inv", cnt);
+  felt* scratch = ctx->buf<felt>("deep_inv_scratch", deep_den_scratch(cnt));
+  const PointMap pm{cx + j0, twn, logn};
+  // the 8th powers: offsets cx^8 and, for n >= 16, the w_{n/8} level of the twiddle table
+  const PointMap pm8{coset_points8(ctx, logn, logB) + j0,
+                     logn > 3 ? ctx->tws(logN) + ((1ull << (logn - 4)) - 1) : nullptr, logn - 3};
+  const felt w8 = root_of_unity(3), w8_2 = sqr(w8);
+  ctx->events(1);
   HIP_CHECK(hipEventRecord(ctx->ev_fork, st));
   HIP_CHECK(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-  launch_deep_denominators(pf, ctx->side, deep_pm, (uint64_t)Bl * n, dt_zz, dt_pw, deep_binv);
+  HIP_CHECK(hipStreamWaitEvent(ctx->copy, ctx->ev_fork, 0));  // the chain's one field inversion runs there
+  launch_deep_denominators(pf, ctx->side, ctx->copy, ctx->up_ev[0], pm, pm8, DeepRoots{w8, w8_2, mul(w8_2, w8)}, cnt,
+                           dt_zz, dt_pw, scratch, deep_inv);
   HIP_CHECK(hipEventRecord(ctx->ev_join, ctx->side));
   dv = ood_launch(ctx, coef, w + C, w, logn, dt_pw, cm);  // composition columns at z only
 }
@@ -406,8 +416,8 @@ void ProofRun::deep_stage() {
     da.w = w; da.C = C; da.logB = logB; da.logn = logn; da.logN = logN;
     da.j0 = j0; da.logBl = logBl;
     da.tlde = tlde; da.clde = clde; da.gamma = dgam; da.dk = dk; da.g = g;
-    da.pm = deep_pm;
-    da.binv = deep_binv;
+    da.inv = deep_inv;
+    da.ginv = deep_ginv(logn);
     HIP_CHECK(hipStreamWaitEvent(st, ctx->ev_join, 0));
     deep_evaluations(ctx, cm, st, da, coef, n, Sj0, logN, deep);
   }

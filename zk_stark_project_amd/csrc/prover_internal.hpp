@@ -534,8 +534,7 @@ struct ProofRun {
   TreeShard ttree, ctree;
   const uint32_t *troot_d = nullptr, *croot_d = nullptr;
   felt wn_root{};
-  felt *deep_binv = nullptr, *dv = nullptr, *dgam = nullptr, *dk = nullptr, *deep = nullptr;
-  PointMap deep_pm{};
+  felt *deep_inv = nullptr, *dv = nullptr, *dgam = nullptr, *dk = nullptr, *deep = nullptr;
   std::vector<felt> ood_trace, ood_comp;  // filled by the host replay of the FRI round trip
   // FRI, grinding, queries
   uint32_t L = 0;
@@ -641,6 +640,8 @@ felt* ood_launch(zkp_ctx* ctx, const felt* arrays, uint32_t narrays, uint32_t nt
 felt* ood_launch_sharded(zkp_ctx* ctx, const felt* arrays, uint32_t narrays, uint32_t ntwo, uint32_t logn,
                          const felt* dpw, zkp_comm* cm, felt* part, felt* dv);
 felt* coset_points(zkp_ctx* ctx, uint32_t logn, uint32_t logB, uint32_t logce);
+const felt* coset_points8(zkp_ctx* ctx, uint32_t logn, uint32_t logB);
+felt deep_ginv(uint32_t logn);
 void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t logB, uint32_t logce, uint32_t u0,
                      uint32_t cel, uint32_t j0, uint32_t logBl, const felt* cx, const felt* twn, const felt* dt_cc,
                      const felt* dt_aval, const felt* tlde, felt* comp, const felt* coef = nullptr,

@@ -116,6 +116,31 @@ felt* coset_points(zkp_ctx* ctx, uint32_t logn, uint32_t logB, uint32_t logce) {
   return cx;
 }
 
+// (g*w_N^j)^8 of every LDE coset j: the coset offsets of the 8th powers of the LDE
+// points, over which the DEEP inverse table is seeded; domain-only, cached per (n, B).
+const felt* coset_points8(zkp_ctx* ctx, uint32_t logn, uint32_t logB) {
+  const uint32_t B = 1u << logB;
+  const std::string key = "coset_x8_" + std::to_string(logn) + "_" + std::to_string(logB);
+  felt* cx8 = ctx->buf<felt>(key, B);
+  if (!ctx->have_cached(key)) {
+    std::vector<felt> h(B);
+    const felt g8 = pow_u64(felt_u64(3), 8), wN8 = pow_u64(root_of_unity(logn + logB), 8);
+    for (uint32_t j = 0; j < B; j++) h[j] = mul(g8, pow_u64(wN8, j));
+    ctx->upload(cx8, h.data(), h.size() * 16);
+  }
+  return cx8;
+}
+
+// w_n^-1 for n = 2^logn (host, computed once)
+felt deep_ginv(uint32_t logn) {
+  static const std::vector<felt> tab = [] {
+    std::vector<felt> t(MAX_LOG_TRACE + 1);
+    for (uint32_t l = 0; l <= MAX_LOG_TRACE; l++) t[l] = inv(root_of_unity(l));
+    return t;
+  }();
+  return tab[logn];
+}
+
 // DefaultConstraintEvaluator::evaluate over the CE cosets [u0, u0 + cel) held by
 // this rank (its LDE cosets are [j0, j0 + 2^logBl)): composition evaluations
 // comp[ul * n + t] = H(g * w_M^(u0+ul) * w_n^t), i.e. CE domain index (u0+ul) + ce*t.

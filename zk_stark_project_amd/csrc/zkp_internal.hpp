@@ -422,13 +422,25 @@ struct DeepArgs {
   const felt* gamma;     // w + C
   const felt* dk;        // device: z, z*w_n, kz, kzg (drawn / formed on the device)
   felt g;
-  PointMap pm;           // x of the shard's LDE points (cx per owned coset)
-  felt* binv;            // scratch: one felt per 2048 LDE points
+  const felt* inv;       // 1 / (x - z) of the shard's LDE points (launch_deep_denominators)
+  felt ginv;             // w_n^-1: 1 / (x_t - z w_n) = ginv * inv[t - 1] within a coset
 };
-// phases 1-2 of the DEEP batch inversion (block inverse products of (x - z)(x - zg)
-// into binv); launch_deep then runs phase 3 + the composition
-void launch_deep_denominators(Prof& prof, hipStream_t s, const PointMap& m, uint64_t count, const felt* zz,
-                              const felt* pw, felt* binv);
+// The DEEP inverse table: table[q] = 1 / (x_q - z) over the `count` points of m
+// (whole cosets, n >= 8), z = zz[0] and pw[l] = z^(2^l) on the device. The 8 points
+// x0 w_8^i of a coset have the product z^8 - x0^8, so only the count/8 values
+// 1 / (y - z^8) go through the three batch-inversion phases, over m8 = the 8th
+// powers of m's points (cx^8, the w_{n/8} table, logn - 3), and one expansion pass
+// makes 8 inverses from each. The phases leave those values scaled by their total
+// product T and invert nothing; the one field inversion, of T in closed form, runs
+// on s2 beside them (s2 must already be ordered after z; ev joins it to s before
+// the expansion). scratch: deep_den_scratch(count) felts.
+struct DeepRoots {
+  felt w8, w8_2, w8_3;   // w_8 = w_n^(n/8), its square and cube
+};
+inline uint64_t deep_den_scratch(uint64_t count) { return count / 8 + count / (8 * 2048) + 2; }
+void launch_deep_denominators(Prof& prof, hipStream_t s, hipStream_t s2, hipEvent_t ev, const PointMap& m,
+                              const PointMap& m8, const DeepRoots& r, uint64_t count, const felt* zz, const felt* pw,
+                              felt* scratch, felt* table);
 void launch_deep(Prof& prof, hipStream_t s, const DeepArgs& a, felt* out);
 // coefficient-form DEEP for wide traces (winterfell combines the trace polynomials
 // before extending): out[p] = sum_{c < w} gamma[c] * coef[c*n + p]
