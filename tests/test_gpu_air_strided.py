@@ -1,6 +1,6 @@
 """Strided assertions (`Assertion::periodic`, `Assertion::sequence`) on the GPU:
-k_eval_program_strided, k_strided_combine, the strided divisor tables and the asserted
-cells of k_check_program (csrc/kernels.hip).
+k_eval_program_strided (eval_program<true>), k_strided_combine, the strided divisor tables
+and the asserted cells of k_check_program (csrc/kernels.hip).
 
 1. Byte anchor: MiMC with its result asserted over the stride n, as a sequence and as a
    periodic assertion, gives the built-in id's proof byte for byte (the built-in id is
@@ -20,9 +20,9 @@ from air_strided_cases import composition_spec, mimc_strided_program, strided_pr
 from option_cases import ALGEBRAIC
 from proof_format import sections
 from test_gpu_options import mimc_inputs
-from zk_stark_project_amd import AIR_MIMC, InvalidTrace, ProofOptions, _native
+from zk_stark_project_amd import AIR_MIMC, AirProgram, InvalidTrace, ProofOptions, _native
 from zk_stark_project_amd._native import verify_status
-from zk_stark_project_amd.field import P, unpack
+from zk_stark_project_amd.field import P, inv, unpack
 
 pytestmark = pytest.mark.gpu
 
@@ -169,6 +169,48 @@ def test_strided_assertions_alone(ctx):
         assert verify_status(prog, proof, [7], opts) == 0
         forged, _ = ctx.prove(prog, trace_array(changed(cols, (1, 4))), [7], opts)
         assert verify_status(prog, forged, [7], opts) != 0
+
+
+def all_registers_program(bump=0):
+    """The program and the one valid column of test_gpu_air_program.test_all_registers_and_ops
+    (8192 ops, 32 registers, a constraint linear in (cur, next)) with singles at steps 0 and 7, a
+    sequence over steps 1 and 5 (its second value plus `bump`) and a periodic assertion at step 2."""
+    p = AirProgram(1)
+    v = [p.cur[0] * p.const(1000 + 7 * i) for i in range(31)]
+    acc = p.next[0]
+    for j in range(4080):
+        acc = acc * p.const(3 + j % 5) + v[j % 31]
+    p.constraint(acc, degree=1)
+    a = p.evaluate([0], [1], 0)[0]  # constraint = a * next + b * cur
+    b = p.evaluate([1], [0], 0)[0]
+    col = [12345]
+    for _ in range(7):
+        col.append(-b * col[-1] % P * inv(a) % P)
+    p.assertion(0, 0, col[0])
+    p.assertion(0, 7, col[7])
+    p.sequence_assertion(0, 1, 4, [col[1], (col[5] + bump) % P])
+    p.periodic_assertion(0, 2, 8, col[2])
+    return p, col
+
+
+def test_all_registers_with_strided_groups(ctx):
+    """32 registers, the largest dynamic LDS (32 KiB per block), through the strided evaluation
+    kernel and through the trace check together with strided cells."""
+    p, col = all_registers_program()
+    cp = p.compile()
+    assert (len(cp.ops), cp.num_registers) == (8192, 32)
+    data = trace_array([col])
+    opts = opts_of(20, 2, 4)
+    with p.register() as prog:
+        assert prog.check_trace(data) is None
+        assert ctx.check_trace(prog, data) is None
+        proof, _ = ctx.prove(prog, data, [1], opts, validate=True)
+        assert verify_status(prog, proof, [1], opts) == 0
+    with all_registers_program(bump=1)[0].register() as prog:
+        got = ctx.check_trace(prog, data)
+        assert got == prog.check_trace(data)
+        assert got[0] == 5 and got[1] is None
+        assert verify_status(prog, proof, [1], opts) != 0
 
 
 # ---------------------------------------------------------------- 4. the device check equals the host's

@@ -401,14 +401,11 @@ int zkp_air_check_trace_device(zkp_ctx* ctx, int air_id, const void* d_trace_col
     if (n > (1ull << MAX_LOG_TRACE)) return (int)ZKP_ERR_TRACE_SHAPE;  // the result key holds 23 bits of row
     const airp::Program& pr = *air.prog;
     HIP_CHECK(hipSetDevice(ctx->device));
-    // the check's device image, in 16-byte units: [ops | constants | periodic descriptors |
-    // raw periodic values | assertion columns | assertion steps | assertion values]. It
+    // the check's device image, in 16-byte units: the code sections (ProgCodeLayout) with the
+    // raw periodic values, then [assertion columns | assertion steps | assertion values]. It
     // depends on the program alone; a context keeps the last id's (ids are never reused).
-    const size_t P = pr.periodic.size(), A = pr.a_col.size();
-    const size_t o_ops = 0, o_const = o_ops + (pr.ops.size() + 1) / 2, o_desc = o_const + pr.consts.size(),
-                 o_tab = o_desc + (P + 1) / 2;
-    size_t o_col = o_tab;
-    for (const auto& col : pr.periodic) o_col += col.size();
+    const ProgCodeLayout lay(pr, 1);
+    const size_t A = pr.a_col.size(), o_col = lay.end();
     // Strided assertions append [cell descriptors (3 units each) | sequence values]; their
     // cell counts and block runs depend on n, so the tag carries it too.
     static_assert(sizeof(ProgStridedCells) == 48, "three 16-byte units");
@@ -426,16 +423,9 @@ int zkp_air_check_trace_device(zkp_ctx* ctx, int air_id, const void* d_trace_col
     if (tag.size() != 1 || !eq(tag[0], want)) {
       tag.clear();
       std::vector<felt> img(total, zero());
-      memcpy(img.data() + o_ops, pr.ops.data(), pr.ops.size() * 8);
-      if (!pr.consts.empty()) memcpy(img.data() + o_const, pr.consts.data(), pr.consts.size() * 16);
-      ProgPeriodic* desc = reinterpret_cast<ProgPeriodic*>(img.data() + o_desc);
-      size_t off = 0;
-      for (size_t p = 0; p < P; p++) {
-        const size_t cyc = pr.periodic[p].size();
-        memcpy(img.data() + o_tab + off, pr.periodic[p].data(), cyc * 16);
-        desc[p] = ProgPeriodic{(uint32_t)off, (uint32_t)(cyc - 1)};
-        off += cyc;
-      }
+      lay.write(img.data());
+      for (size_t p = 0; p < pr.periodic.size(); p++)
+        memcpy(img.data() + lay.tab[p], pr.periodic[p].data(), pr.periodic[p].size() * 16);
       uint32_t* steps = reinterpret_cast<uint32_t*>(img.data() + o_step);
       for (size_t k = 0; k < A; k++) steps[k] = (uint32_t)pr.a_step[k];  // < n <= 2^23 (build_air)
       if (A) {
@@ -459,13 +449,8 @@ int zkp_air_check_trace_device(zkp_ctx* ctx, int air_id, const void* d_trace_col
       tag.assign(1, want);
     }
     ProgCheckArgs ca{};
-    ca.ops = reinterpret_cast<const uint64_t*>(dimg + o_ops);
-    ca.nops = (uint32_t)pr.ops.size();
-    ca.nreg = pr.nreg;
+    ca.code = lay.code(dimg);
     ca.nassert = (uint32_t)A;
-    ca.consts = dimg + o_const;
-    ca.per_desc = reinterpret_cast<const ProgPeriodic*>(dimg + o_desc);
-    ca.per_tab = dimg + o_tab;
     ca.a_col = reinterpret_cast<const uint32_t*>(dimg + o_col);
     ca.a_step = reinterpret_cast<const uint32_t*>(dimg + o_step);
     ca.a_val = dimg + o_val;

@@ -2,7 +2,7 @@
 // validated copy of a constraint program, the process-wide table of registered
 // ids, and the host interpreter that the verifier (OOD frame) and
 // zkp_air_check_trace (trace rows) share. The device runs the same op stream in
-// k_eval_program (kernels.hip). Pure host code: no HIP calls.
+// run_program (kernels.hip). Pure host code: no HIP calls.
 #pragma once
 #include <algorithm>
 #include <map>
@@ -13,16 +13,10 @@
 
 #include "../../include/zkp.h"
 #include "felt.hpp"
+#include "zkp_internal.hpp"  // op_code, op_dst, op_a, op_b, src_kind, src_index
 
 namespace airp {
 using namespace fp;
-
-inline uint32_t op_code(uint64_t op) { return (uint32_t)(op & 0xff); }
-inline uint32_t op_dst(uint64_t op) { return (uint32_t)((op >> 8) & 0xff); }
-inline uint32_t op_a(uint64_t op) { return (uint32_t)((op >> 16) & 0xffff); }
-inline uint32_t op_b(uint64_t op) { return (uint32_t)((op >> 32) & 0xffff); }
-inline uint32_t src_kind(uint32_t operand) { return operand >> 13; }
-inline uint32_t src_index(uint32_t operand) { return operand & 0x1fff; }
 
 // a strided assertion (zkp_air_strided_assertion): T[col][first + stride*i] = val (periodic,
 // `values` empty) or values[i] (sequence)

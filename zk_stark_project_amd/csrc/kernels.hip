@@ -426,137 +426,90 @@ __global__ __launch_bounds__(TPB) void k_eval_mimc(EvalCommon c, MimcEvalArgs a,
   });
 }
 
-// A registered constraint program (include/zkp.h zkp_air_program) at one CE point
-// per thread. The op stream, the constants, the coefficients and the assertion
+// The interpreter of a registered constraint program (include/zkp.h zkp_air_program),
+// one frame per thread. The op stream, the constants, the coefficients and the assertion
 // tables are the same for every lane: their addresses are built from kernel
 // arguments and loop counters only, so they come through uniform (scalar) loads and
 // the opcode / operand-kind switches are scalar branches. The program's registers
 // live in LDS as [register][thread], 16 bytes per lane and contiguous over the wave
 // (ds_read_b128 / ds_write_b128, one 16-byte slot per lane: conflict-free), sized at
 // launch from the program's register count: PROG_TPB * 16 * nreg bytes per block of
-// one wave. No lane reads another lane's slot, so the kernel has no barrier.
+// one wave. No lane reads another lane's slot, so the kernels have no barrier.
 // Field ops are the canonical add / sub / mul: every value written is canonical.
 constexpr uint32_t PROG_TPB = 64;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
 
-__global__ __launch_bounds__(PROG_TPB) void k_eval_program(EvalCommon c, ProgEvalArgs a, const felt* __restrict__ lde,
-                                                           felt* __restrict__ comp) {
+// register r of this lane: rg[r * PROG_TPB]. The pointer keeps its LDS address space, so
+// a register operand is a ds_read_b128 and never merges with the global loads into a flat one
+__device__ __forceinline__ lds_u32x4* prog_regs() {
   extern __shared__ __align__(16) unsigned char prog_lds[];
-  // register r of this lane: rg[r * PROG_TPB]. The pointer keeps its LDS address space, so
-  // a register operand is a ds_read_b128 and never merges with the global loads into a flat one
-  lds_u32x4* const rg = (lds_u32x4*)prog_lds + threadIdx.x;
-  const uint64_t M = (uint64_t)c.cel << c.logn;
-  const uint64_t q = (uint64_t)blockIdx.x * PROG_TPB + threadIdx.x;
-  if (q >= M) return;
-  const CePoint pt = ce_point(c, q);
-  const felt* const cur = lde + pt.off;
-  const felt* const nxt = lde + pt.off_next;
-  auto fetch = [&](uint32_t operand) -> felt {
-    const uint32_t idx = operand & 0x1fff;
-    switch (operand >> 13) {
-      case ZKP_SRC_REG: {
-        const u32x4 r = rg[idx * PROG_TPB];
-        return make((uint64_t)r.x | ((uint64_t)r.y << 32), (uint64_t)r.z | ((uint64_t)r.w << 32));
-      }
-      case ZKP_SRC_CUR: return cur[idx * a.col_stride];
-      case ZKP_SRC_NEXT: return nxt[idx * a.col_stride];
-      case ZKP_SRC_PERIODIC: {
-        const ProgPeriodic d = a.per_desc[idx];
-        return a.per_tab[d.off + ((uint32_t)pt.s & d.mask)];
-      }
-      default: return a.consts[idx];
-    }
-  };
-  // transition part: T = sum_i cc[i] * t_i (an EMIT is a product with its coefficient)
-  felt T = zero();
-  uint32_t emitted = 0;
-  for (uint32_t pc = 0; pc < a.nops; pc++) {
-    const uint64_t op = a.ops[pc];
-    const uint32_t code = (uint32_t)op & 0xff;
-    const felt x = fetch((uint32_t)(op >> 16) & 0xffff);
-    const felt y = code == ZKP_OP_EMIT ? a.cc[emitted] : fetch((uint32_t)(op >> 32) & 0xffff);
-    felt r;
-    if (code == ZKP_OP_ADD) r = add(x, y);
-    else if (code == ZKP_OP_SUB) r = sub(x, y);
-    else r = mul(x, y);
-    if (code == ZKP_OP_EMIT) {
-      T = add(T, r);
-      emitted++;
-    } else {
-      u32x4 w;
-      w.x = (uint32_t)r.lo; w.y = (uint32_t)(r.lo >> 32); w.z = (uint32_t)r.hi; w.w = (uint32_t)(r.hi >> 32);
-      rg[((uint32_t)(op >> 8) & 0xff) * PROG_TPB] = w;
-    }
-  }
-  const felt px = point_x(c.pm, q);
-  felt v = mul(mul(T, sub(px, c.w_last)), c.zinv[pt.u]);
-  // boundary part, one divisor table per group of assertions that share a step
-  const felt* const bcc = a.cc + a.num_t;
-  uint32_t k = 0;
-  static_for<0, (int)PROG_MAX_GROUPS>([&](auto g) {
-    if ((uint32_t)g < a.ngroups) {
-      felt s = zero();
-      for (; k < a.grp_end[g]; k++) s = add(s, mul(bcc[k], sub(cur[a.a_col[k] * a.col_stride], a.a_val[k])));
-      v = add(v, mul(s, a.dinv[g][q]));
-    }
-  });
-  comp[q] = v;
+  return (lds_u32x4*)prog_lds + threadIdx.x;
+}
+__device__ __forceinline__ felt reg_load(const lds_u32x4* rg, uint32_t r) {
+  const u32x4 v = rg[r * PROG_TPB];
+  return make((uint64_t)v.x | ((uint64_t)v.y << 32), (uint64_t)v.z | ((uint64_t)v.w << 32));
+}
+__device__ __forceinline__ void reg_store(lds_u32x4* rg, uint32_t r, felt v) {
+  u32x4 w;
+  w.x = (uint32_t)v.lo; w.y = (uint32_t)(v.lo >> 32); w.z = (uint32_t)v.hi; w.w = (uint32_t)(v.hi >> 32);
+  rg[r * PROG_TPB] = w;
 }
 
-// k_eval_program written out again for a program with strided assertions (ProgStridedArgs): the
-// same interpreter and single-step groups, then the strided groups. A program without them
-// launches k_eval_program, whose code is what it was before they existed.
-__global__ __launch_bounds__(PROG_TPB) void k_eval_program_strided(EvalCommon c, ProgEvalArgs a, ProgStridedArgs sa,
-                                                                   const felt* __restrict__ lde,
-                                                                   felt* __restrict__ comp) {
-  extern __shared__ __align__(16) unsigned char prog_lds[];
-  // register r of this lane: rg[r * PROG_TPB]. The pointer keeps its LDS address space, so
-  // a register operand is a ds_read_b128 and never merges with the global loads into a flat one
-  lds_u32x4* const rg = (lds_u32x4*)prog_lds + threadIdx.x;
+// CUR / NEXT column i is cur[i * stride] / nxt[i * stride]; a periodic column is read at
+// (per_index & its mask). WEIGHTED (evaluation): EMIT i hands emit(i, cc[i] * operand), the
+// product going through the same mul as a MUL op. Otherwise (the trace check): emit(i, operand).
+template <bool WEIGHTED, class Emit>
+__device__ __forceinline__ void run_program(const ProgCode& p, lds_u32x4* rg, const felt* cur, const felt* nxt,
+                                            uint64_t stride, uint32_t per_index, const felt* cc, Emit&& emit) {
+  auto fetch = [&](uint32_t operand) -> felt {
+    const uint32_t idx = airp::src_index(operand);
+    switch (airp::src_kind(operand)) {
+      case ZKP_SRC_REG: return reg_load(rg, idx);
+      case ZKP_SRC_CUR: return cur[idx * stride];
+      case ZKP_SRC_NEXT: return nxt[idx * stride];
+      case ZKP_SRC_PERIODIC: {
+        const ProgPeriodic d = p.per_desc[idx];
+        return p.per_tab[d.off + (per_index & d.mask)];
+      }
+      default: return p.consts[idx];
+    }
+  };
+  uint32_t emitted = 0;
+  for (uint32_t pc = 0; pc < p.nops; pc++) {
+    const uint64_t op = p.ops[pc];
+    const uint32_t code = airp::op_code(op);
+    const felt x = fetch(airp::op_a(op));
+    if constexpr (!WEIGHTED) {
+      if (code == ZKP_OP_EMIT) {
+        emit(emitted++, x);
+        continue;
+      }
+    }
+    const felt y = WEIGHTED && code == ZKP_OP_EMIT ? cc[emitted] : fetch(airp::op_b(op));
+    felt r;
+    if (code == ZKP_OP_ADD) r = add(x, y);
+    else if (code == ZKP_OP_SUB) r = sub(x, y);
+    else r = mul(x, y);
+    if (WEIGHTED && code == ZKP_OP_EMIT) emit(emitted++, r);
+    else reg_store(rg, airp::op_dst(op), r);
+  }
+}
+
+// A program at one CE point per thread: T = sum_i cc[i] * t_i over Z_T, the single-step
+// assertion groups, and with STRIDED the strided groups (ProgStridedArgs) after them.
+template <bool STRIDED>
+__device__ __forceinline__ void eval_program(const EvalCommon& c, const ProgEvalArgs& a, const ProgStridedArgs* sa,
+                                             const felt* __restrict__ lde, felt* __restrict__ comp) {
+  lds_u32x4* const rg = prog_regs();
   const uint64_t M = (uint64_t)c.cel << c.logn;
   const uint64_t q = (uint64_t)blockIdx.x * PROG_TPB + threadIdx.x;
   if (q >= M) return;
   const CePoint pt = ce_point(c, q);
   const felt* const cur = lde + pt.off;
-  const felt* const nxt = lde + pt.off_next;
-  auto fetch = [&](uint32_t operand) -> felt {
-    const uint32_t idx = operand & 0x1fff;
-    switch (operand >> 13) {
-      case ZKP_SRC_REG: {
-        const u32x4 r = rg[idx * PROG_TPB];
-        return make((uint64_t)r.x | ((uint64_t)r.y << 32), (uint64_t)r.z | ((uint64_t)r.w << 32));
-      }
-      case ZKP_SRC_CUR: return cur[idx * a.col_stride];
-      case ZKP_SRC_NEXT: return nxt[idx * a.col_stride];
-      case ZKP_SRC_PERIODIC: {
-        const ProgPeriodic d = a.per_desc[idx];
-        return a.per_tab[d.off + ((uint32_t)pt.s & d.mask)];
-      }
-      default: return a.consts[idx];
-    }
-  };
-  // transition part: T = sum_i cc[i] * t_i (an EMIT is a product with its coefficient)
   felt T = zero();
-  uint32_t emitted = 0;
-  for (uint32_t pc = 0; pc < a.nops; pc++) {
-    const uint64_t op = a.ops[pc];
-    const uint32_t code = (uint32_t)op & 0xff;
-    const felt x = fetch((uint32_t)(op >> 16) & 0xffff);
-    const felt y = code == ZKP_OP_EMIT ? a.cc[emitted] : fetch((uint32_t)(op >> 32) & 0xffff);
-    felt r;
-    if (code == ZKP_OP_ADD) r = add(x, y);
-    else if (code == ZKP_OP_SUB) r = sub(x, y);
-    else r = mul(x, y);
-    if (code == ZKP_OP_EMIT) {
-      T = add(T, r);
-      emitted++;
-    } else {
-      u32x4 w;
-      w.x = (uint32_t)r.lo; w.y = (uint32_t)(r.lo >> 32); w.z = (uint32_t)r.hi; w.w = (uint32_t)(r.hi >> 32);
-      rg[((uint32_t)(op >> 8) & 0xff) * PROG_TPB] = w;
-    }
-  }
+  run_program<true>(a.code, rg, cur, lde + pt.off_next, a.col_stride, (uint32_t)pt.s, a.cc,
+                    [&](uint32_t, felt t) { T = add(T, t); });
   const felt px = point_x(c.pm, q);
   felt v = mul(mul(T, sub(px, c.w_last)), c.zinv[pt.u]);
   // boundary part, one divisor table per group of assertions that share a step
@@ -572,16 +525,29 @@ __global__ __launch_bounds__(PROG_TPB) void k_eval_program_strided(EvalCommon c,
   // strided groups: sum_k cc_k (cur[col_k] - val_k) - W_g, W_g = sum over the group's sequences of
   // cc_j V_j (k_strided_combine, extended to the CE cosets), over x^k - w^(first k): a table of
   // stride * ce inverses read at the CE index modulo its length, as the periodic columns are
-  uint32_t j = 0;
-  static_for<0, (int)PROG_MAX_STRIDED_GROUPS>([&](auto g) {
-    if ((uint32_t)g < sa.ngroups) {
-      felt s = zero();
-      for (; j < sa.grp_end[g]; j++) s = add(s, mul(sa.cc[j], sub(cur[sa.col[j] * a.col_stride], sa.val[j])));
-      if (sa.W[g]) s = sub(s, sa.W[g][q]);
-      v = add(v, mul(s, sa.dtab[g][(uint32_t)pt.s & sa.mask[g]]));
-    }
-  });
+  if constexpr (STRIDED) {
+    uint32_t j = 0;
+    static_for<0, (int)PROG_MAX_STRIDED_GROUPS>([&](auto g) {
+      if ((uint32_t)g < sa->ngroups) {
+        felt s = zero();
+        for (; j < sa->grp_end[g]; j++) s = add(s, mul(sa->cc[j], sub(cur[sa->col[j] * a.col_stride], sa->val[j])));
+        if (sa->W[g]) s = sub(s, sa->W[g][q]);
+        v = add(v, mul(s, sa->dtab[g][(uint32_t)pt.s & sa->mask[g]]));
+      }
+    });
+  }
   comp[q] = v;
+}
+
+// Two entry points, so that a program without strided assertions carries no ProgStridedArgs
+__global__ __launch_bounds__(PROG_TPB) void k_eval_program(EvalCommon c, ProgEvalArgs a, const felt* __restrict__ lde,
+                                                           felt* __restrict__ comp) {
+  eval_program<false>(c, a, nullptr, lde, comp);
+}
+__global__ __launch_bounds__(PROG_TPB) void k_eval_program_strided(EvalCommon c, ProgEvalArgs a, ProgStridedArgs sa,
+                                                                   const felt* __restrict__ lde,
+                                                                   felt* __restrict__ comp) {
+  eval_program<true>(c, a, &sa, lde, comp);
 }
 
 // W_g = sum_j cc_j V_j over the sequences j of strided group g = blockIdx.y, as one coefficient
@@ -606,11 +572,9 @@ __global__ __launch_bounds__(TPB) void k_strided_combine(ProgSeqArgs a, uint32_t
 // A natural (column-major, not extended) trace against a registered constraint
 // program: what zkp_air_check_trace does on the host. Blocks [0, frame_blocks) take one
 // frame (rows r, r + 1) per thread, r in [0, n - 2]: row n - 1 starts no frame and nothing
-// wraps to row 0, so a lane with r >= n - 1 returns before its first load. The
-// interpreter is k_eval_program's (uniform op / constant fetches, registers in LDS as
-// [register][thread], one wave per block, canonical field ops) with three differences:
-// CUR / NEXT read T[c*n + r] / T[c*n + r + 1], PERIODIC reads the column's raw value
-// per_tab[off + (r & (cycle - 1))], and an EMIT tests its operand against zero. A lane
+// wraps to row 0, so a lane with r >= n - 1 returns before its first load. run_program
+// with CUR / NEXT reading T[c*n + r] / T[c*n + r + 1], PERIODIC the column's raw value
+// per_tab[off + (r & (cycle - 1))], and an EMIT testing its operand against zero. A lane
 // keeps the index of its first non-zero EMIT and still runs the stream to its end (the
 // stream is wave-uniform). Keys (r << 10) | constraint grow with the lane, so the
 // wave's minimum is the key of its lowest failing lane (one ballot); that lane alone
@@ -622,7 +586,6 @@ __global__ __launch_bounds__(TPB) void k_strided_combine(ProgSeqArgs a, uint32_t
 // host reads the first failing assertion in stored order and its lowest failing row.
 __global__ __launch_bounds__(PROG_TPB) void k_check_program(ProgCheckArgs a, const felt* __restrict__ T,
                                                             unsigned long long* __restrict__ res) {
-  extern __shared__ __align__(16) unsigned char check_lds[];
   if (blockIdx.x >= a.frame_blocks) {
     const uint32_t ab = blockIdx.x - a.frame_blocks;
     bool fail = false;
@@ -656,46 +619,14 @@ __global__ __launch_bounds__(PROG_TPB) void k_check_program(ProgCheckArgs a, con
     if (failing && threadIdx.x == (uint32_t)__builtin_ctzll(failing)) atomicMin(res + 1, key);
     return;
   }
-  lds_u32x4* const rg = (lds_u32x4*)check_lds + threadIdx.x;
+  lds_u32x4* const rg = prog_regs();
   const uint64_t r = (uint64_t)blockIdx.x * PROG_TPB + threadIdx.x;
   if (r + 1 >= a.n) return;
-  const felt* const cur = T + r;
-  auto fetch = [&](uint32_t operand) -> felt {
-    const uint32_t idx = operand & 0x1fff;
-    switch (operand >> 13) {
-      case ZKP_SRC_REG: {
-        const u32x4 v = rg[idx * PROG_TPB];
-        return make((uint64_t)v.x | ((uint64_t)v.y << 32), (uint64_t)v.z | ((uint64_t)v.w << 32));
-      }
-      case ZKP_SRC_CUR: return cur[idx * a.n];
-      case ZKP_SRC_NEXT: return cur[idx * a.n + 1];
-      case ZKP_SRC_PERIODIC: {
-        const ProgPeriodic d = a.per_desc[idx];
-        return a.per_tab[d.off + ((uint32_t)r & d.mask)];
-      }
-      default: return a.consts[idx];
-    }
-  };
   constexpr uint32_t NONE = 0xffffffffu;
-  uint32_t bad = NONE, emitted = 0;
-  for (uint32_t pc = 0; pc < a.nops; pc++) {
-    const uint64_t op = a.ops[pc];
-    const uint32_t code = (uint32_t)op & 0xff;
-    const felt x = fetch((uint32_t)(op >> 16) & 0xffff);
-    if (code == ZKP_OP_EMIT) {
-      if (bad == NONE && !is_zero(x)) bad = emitted;
-      emitted++;
-      continue;
-    }
-    const felt y = fetch((uint32_t)(op >> 32) & 0xffff);
-    felt v;
-    if (code == ZKP_OP_ADD) v = add(x, y);
-    else if (code == ZKP_OP_SUB) v = sub(x, y);
-    else v = mul(x, y);
-    u32x4 w;
-    w.x = (uint32_t)v.lo; w.y = (uint32_t)(v.lo >> 32); w.z = (uint32_t)v.hi; w.w = (uint32_t)(v.hi >> 32);
-    rg[((uint32_t)(op >> 8) & 0xff) * PROG_TPB] = w;
-  }
+  uint32_t bad = NONE;
+  run_program<false>(a.code, rg, T + r, T + r + 1, a.n, (uint32_t)r, nullptr, [&](uint32_t i, felt t) {
+    if (bad == NONE && !is_zero(t)) bad = i;
+  });
   const uint64_t failing = __builtin_amdgcn_ballot_w64(bad != NONE);
   if (failing && threadIdx.x == (uint32_t)__builtin_ctzll(failing))
     atomicMin(res, (unsigned long long)((r << 10) | bad));
@@ -1603,15 +1534,19 @@ void launch_eval_mimc(Prof& prof, hipStream_t s, const EvalCommon& c, const Mimc
                             a.dinv, comp));
 }
 
+// dynamic LDS of a launch that runs a program: its registers, [register][thread] (16 bytes per lane)
+static size_t prog_lds_bytes(const ProgCode& p, const char* what) {
+  if (p.nreg == 0 || p.nreg > ZKP_AIR_MAX_REGISTERS) launch_fail(ZKP_ERR_ARGUMENT, what);
+  return (size_t)p.nreg * PROG_TPB * sizeof(felt);
+}
+
 void launch_eval_program(Prof& prof, hipStream_t s, const EvalCommon& c, const ProgEvalArgs& a, const felt* lde,
                          felt* comp, const ProgStridedArgs* sa) {
   const uint64_t M = (uint64_t)c.cel << c.logn;
-  if (a.nreg == 0 || a.nreg > ZKP_AIR_MAX_REGISTERS || a.ngroups > PROG_MAX_GROUPS)
-    launch_fail(ZKP_ERR_ARGUMENT, "constraint program outside the kernel's limits");
+  const size_t lds = prog_lds_bytes(a.code, "constraint program outside the kernel's limits");
+  if (a.ngroups > PROG_MAX_GROUPS) launch_fail(ZKP_ERR_ARGUMENT, "constraint program outside the kernel's limits");
   for (uint32_t g = 0; g < a.ngroups; g++)
     if (!a.dinv_ready[g]) launch_den_table(prof, s, c.pm, M, a.w_step[g], zero(), 0, a.binv, a.dinv[g]);
-  // LDS: the program's registers, [register][thread] (16 bytes per lane)
-  const size_t lds = (size_t)a.nreg * PROG_TPB * sizeof(felt);
   if (sa && sa->ngroups) {
     if (sa->ngroups > PROG_MAX_STRIDED_GROUPS)
       launch_fail(ZKP_ERR_ARGUMENT, "constraint program outside the kernel's limits");
@@ -1640,15 +1575,14 @@ void launch_strided_combine(Prof& prof, hipStream_t s, const ProgSeqArgs& a, uin
 
 void launch_check_program(Prof& prof, hipStream_t s, ProgCheckArgs a, uint32_t width, const felt* T,
                           unsigned long long* res, uint64_t strided_blocks) {
-  if (a.nreg == 0 || a.nreg > ZKP_AIR_MAX_REGISTERS || a.nassert > ZKP_AIR_MAX_ASSERTIONS || a.n < 2 ||
-      a.n > (1ull << MAX_LOG_TRACE))
+  const size_t lds = prog_lds_bytes(a.code, "trace check outside the kernel's limits");
+  if (a.nassert > ZKP_AIR_MAX_ASSERTIONS || a.n < 2 || a.n > (1ull << MAX_LOG_TRACE))
     launch_fail(ZKP_ERR_ARGUMENT, "trace check outside the kernel's limits");
   a.frame_blocks = blocks_for(a.n - 1, PROG_TPB);
   a.single_blocks = blocks_for(a.nassert, PROG_TPB);
   const uint64_t all = (uint64_t)a.frame_blocks + a.single_blocks + strided_blocks;
   if (all >> 31) launch_fail(ZKP_ERR_ARGUMENT, "trace check outside the kernel's limits");
   const uint32_t blocks = (uint32_t)all;
-  const size_t lds = (size_t)a.nreg * PROG_TPB * sizeof(felt);
   LAUNCH(prof, "check_program", s, (double)width * (double)a.n * 16.0,
          hipLaunchKernelGGL(k_check_program, dim3(blocks), dim3(PROG_TPB), lds, s, a, T, res));
 }

@@ -385,6 +385,35 @@ struct zkp_ctx {
 // a context on `device` with its streams and events (nullptr on failure)
 zkp_ctx* new_ctx(int device);
 
+// The sections that every device image of a registered program starts with, in 16-byte
+// units: [ops | constants | periodic descriptors | periodic tables], column p's table of
+// cycle_p * scale felts at unit tab[p]. write() fills all but the tables' contents, which
+// are the caller's (scale = ce: the column over the CE domain; 1: its raw cycle), as are
+// the sections it appends from end() on.
+struct ProgCodeLayout {
+  const airp::Program& pr;
+  size_t o_const, o_desc;
+  std::vector<size_t> tab;
+  ProgCodeLayout(const airp::Program& program, size_t scale) : pr(program) {
+    o_const = (pr.ops.size() + 1) / 2;
+    o_desc = o_const + pr.consts.size();
+    tab.push_back(o_desc + (pr.periodic.size() + 1) / 2);
+    for (const auto& col : pr.periodic) tab.push_back(tab.back() + col.size() * scale);
+  }
+  size_t end() const { return tab.back(); }
+  void write(felt* img) const {
+    memcpy(img, pr.ops.data(), pr.ops.size() * 8);
+    if (!pr.consts.empty()) memcpy(img + o_const, pr.consts.data(), pr.consts.size() * 16);
+    ProgPeriodic* desc = reinterpret_cast<ProgPeriodic*>(img + o_desc);
+    for (size_t p = 0; p + 1 < tab.size(); p++)
+      desc[p] = ProgPeriodic{(uint32_t)(tab[p] - tab[0]), (uint32_t)(tab[p + 1] - tab[p] - 1)};
+  }
+  ProgCode code(const felt* dimg) const {
+    return ProgCode{reinterpret_cast<const uint64_t*>(dimg), (uint32_t)pr.ops.size(), pr.nreg, dimg + o_const,
+                    reinterpret_cast<const ProgPeriodic*>(dimg + o_desc), dimg + tab[0]};
+  }
+};
+
 namespace zkpi {
 
 // ------------------------------------------------------------------ sharded commitments

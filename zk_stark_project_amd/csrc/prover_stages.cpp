@@ -193,13 +193,13 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
     // a registered constraint program: k_eval_program reads the coefficients from dt_cc as drawn
     if (!cel) return;
     const airp::Program& pr = *air.prog;
-    // the program's device image, in 16-byte units: [ops | constants | assertion columns |
-    // periodic descriptors | periodic tables]. A context keeps one image, the last
+    // the program's device image, in 16-byte units: the code sections (ProgCodeLayout), then
+    // the assertion columns. A context keeps one image, the last
     // (id, n, ce) it evaluated (ids are never reused): proving another instance replaces it,
     // so registering and freeing ids does not grow the context.
     // Periodic column of cycle c over the CE domain: interpolate over <w_c>, evaluate at
     // g^(n/c) * <w_{c ce}> (as kper_* below), indexed by the CE index mod c*ce.
-    const size_t P = pr.periodic.size();
+    const ProgCodeLayout lay(pr, ce);
     // Strided assertions append [columns | values | sequence descriptors | sequence tables]:
     // per sequence the k coefficients of V_j, interpolated over <w_k>, twisted by
     // w_n^(-first i) and multiplied by n (the coefficient layout k_strided_combine writes).
@@ -208,12 +208,8 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
     size_t nseq = 0, seq_felts = 0;
     for (const airp::Strided& a : sv)
       if (a.sequence()) nseq++, seq_felts += a.values.size();
-    const size_t o_ops = 0, o_const = o_ops + (pr.ops.size() + 1) / 2, o_col = o_const + pr.consts.size(),
-                 o_desc = o_col + (pr.a_col.size() + 3) / 4, o_tab = o_desc + (P + 1) / 2;
-    size_t o_scol = o_tab;
-    for (const auto& col : pr.periodic) o_scol += col.size() * ce;
-    const size_t o_sval = o_scol + (S + 3) / 4, o_sdesc = o_sval + S, o_stab = o_sdesc + (nseq + 1) / 2,
-                 total = o_stab + seq_felts;
+    const size_t o_col = lay.end(), o_scol = o_col + (pr.a_col.size() + 3) / 4, o_sval = o_scol + (S + 3) / 4,
+                 o_sdesc = o_sval + S, o_stab = o_sdesc + (nseq + 1) / 2, total = o_stab + seq_felts;
     felt* dimg = ctx->buf<felt>("prog_image", total);
     std::vector<felt>& img = ctx->host_cache["prog_image"];  // kept: a large image is copied from it asynchronously
     std::vector<felt>& tag = ctx->host_cache["prog_image_tag"];
@@ -221,19 +217,14 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
     if (tag.size() != 2 || !eq(tag[0], want[0]) || !eq(tag[1], want[1])) {
       tag.clear();
       img.assign(total, zero());
-      memcpy(img.data() + o_ops, pr.ops.data(), pr.ops.size() * 8);
-      if (!pr.consts.empty()) memcpy(img.data() + o_const, pr.consts.data(), pr.consts.size() * 16);
+      lay.write(img.data());
       if (!pr.a_col.empty()) memcpy(img.data() + o_col, pr.a_col.data(), pr.a_col.size() * 4);
-      ProgPeriodic* desc = reinterpret_cast<ProgPeriodic*>(img.data() + o_desc);
-      size_t off = 0;
-      for (size_t p = 0; p < P; p++) {
+      for (size_t p = 0; p < pr.periodic.size(); p++) {
         const size_t cyc = pr.periodic[p].size();
         std::vector<felt> kc = pr.periodic[p];
         host_interpolate(kc, one());
         const std::vector<felt> kv = host_evaluate(kc, cyc * ce, pow_u64(g, n / cyc));
-        memcpy(img.data() + o_tab + off, kv.data(), kv.size() * 16);
-        desc[p] = ProgPeriodic{(uint32_t)off, (uint32_t)(cyc * ce - 1)};
-        off += kv.size();
+        memcpy(img.data() + lay.tab[p], kv.data(), kv.size() * 16);
       }
       uint32_t* scol = reinterpret_cast<uint32_t*>(img.data() + o_scol);
       ProgSeq* sdesc = reinterpret_cast<ProgSeq*>(img.data() + o_sdesc);
@@ -258,14 +249,9 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
     }
     ec.zinv = dz;
     ProgEvalArgs pa{};
-    pa.ops = reinterpret_cast<const uint64_t*>(dimg + o_ops);
-    pa.nops = (uint32_t)pr.ops.size();
-    pa.nreg = pr.nreg;
+    pa.code = lay.code(dimg);
     pa.num_t = pr.num_t;
-    pa.consts = dimg + o_const;
     pa.a_col = reinterpret_cast<const uint32_t*>(dimg + o_col);
-    pa.per_desc = reinterpret_cast<const ProgPeriodic*>(dimg + o_desc);
-    pa.per_tab = dimg + o_tab;
     pa.cc = dt_cc;
     pa.a_val = dt_aval;
     pa.col_stride = n << logBl;

@@ -277,19 +277,36 @@ void launch_lin_lincomb(Prof& prof, hipStream_t s, bool trans, bool two, const f
 void launch_eval_linear_pts(Prof& prof, hipStream_t s, const EvalCommon& c, const LinearEvalArgs& a, const felt* ev,
                             felt* comp);
 
-// A registered constraint program (include/zkp.h zkp_air_program; k_eval_program):
+// The fields of an op and of an operand (include/zkp.h zkp_air_program), for the host
+// interpreter and validation (air_program.hpp) and the device interpreter (kernels.hip)
+namespace airp {
+constexpr uint32_t op_code(uint64_t op) { return (uint32_t)(op & 0xff); }
+constexpr uint32_t op_dst(uint64_t op) { return (uint32_t)((op >> 8) & 0xff); }
+constexpr uint32_t op_a(uint64_t op) { return (uint32_t)((op >> 16) & 0xffff); }
+constexpr uint32_t op_b(uint64_t op) { return (uint32_t)((op >> 32) & 0xffff); }
+constexpr uint32_t src_kind(uint32_t operand) { return operand >> 13; }
+constexpr uint32_t src_index(uint32_t operand) { return operand & 0x1fff; }
+}  // namespace airp
+
+// A registered constraint program's code on the device, as the interpreter of kernels.hip
+// (run_program) reads it; the host lays it out with ProgCodeLayout (prover_internal.hpp)
+struct ProgPeriodic {
+  uint32_t off, mask;    // column's table at per_tab + off, indexed by (periodic index & mask), mask = table length - 1
+};
+struct ProgCode {
+  const uint64_t* ops;   // device: the op stream (read through uniform loads)
+  uint32_t nops, nreg;
+  const felt* consts;    // device: the constant pool
+  const ProgPeriodic* per_desc;  // device: one per periodic column
+  const felt* per_tab;   // device: the periodic columns' tables
+};
+// A program over the CE domain (k_eval_program):
 // the op stream runs once per CE point, T = sum_i cc[i] * t_i over Z_T, then per group
 // of assertions that share a step sum_k cc[num_t + k] * (cur[col_k] - val_k) over (x - w^step).
 constexpr uint32_t PROG_MAX_GROUPS = 4;  // ZKP_AIR_MAX_ASSERTION_STEPS
-struct ProgPeriodic {
-  uint32_t off, mask;    // column's table at per_tab + off, indexed by (CE index & mask), mask = cycle*ce - 1
-};
 struct ProgEvalArgs {
-  const uint64_t* ops;   // device: the op stream (read through uniform loads)
-  uint32_t nops, nreg, num_t, ngroups;
-  const felt* consts;    // device: the constant pool
-  const ProgPeriodic* per_desc;  // device: one per periodic column
-  const felt* per_tab;   // device: the periodic columns over the CE domain
+  ProgCode code;         // periodic tables over the CE domain, indexed by the CE index (mask = cycle*ce - 1)
+  uint32_t num_t, ngroups;
   const uint32_t* a_col; // device: assertion columns, sorted by (step, column)
   const felt* cc;        // device: num_t transition then the assertion coefficients
   const felt* a_val;     // device: assertion values
@@ -302,7 +319,7 @@ struct ProgEvalArgs {
 };
 // A program's strided assertions (include/zkp.h zkp_air_strided_assertion), in stored order
 // (stride, first, column); a group shares (stride, first) and the divisor x^k - w_n^(first k),
-// k = n / stride. k_eval_program_strided adds, per group,
+// k = n / stride. k_eval_program_strided (eval_program<true>) adds, per group,
 //   (sum_j cc_j * (cur[col_j] - val_j) - W_g[q]) * dtab_g[CE index & mask_g]
 // after the single-step groups: val_j = 0 for a sequence, whose values enter through
 // W_g = sum_j cc_j V_j (launch_strided_combine, then the coset NTT), null for a group of
@@ -318,7 +335,7 @@ struct ProgStridedArgs {
   const felt* val;       // device: their values (zero for a sequence)
   const felt* cc;        // device: the coefficient of the first strided assertion
 };
-// `sa` (nullable): with strided groups the launch is k_eval_program_strided
+// `sa` (nullable): with strided groups the launch is k_eval_program_strided, the same body with them
 void launch_eval_program(Prof& prof, hipStream_t s, const EvalCommon& c, const ProgEvalArgs& a, const felt* lde,
                          felt* comp, const ProgStridedArgs* sa = nullptr);
 // table[s] = 1/(gk[0] * w_l^s - c0) for s < l = 2^logl (gk: one device felt, g^k; twl[j] = w_l^j,
@@ -352,14 +369,11 @@ struct ProgStridedCells {
   felt val;
 };
 struct ProgCheckArgs {
-  const uint64_t* ops;   // device: the op stream
-  uint32_t nops, nreg, nassert, frame_blocks;  // nassert: the singles; frame_blocks: set by the launcher
-  uint32_t single_blocks, nstrided;            // single_blocks: set by the launcher
+  ProgCode code;         // periodic tables: the columns' raw values, indexed by the row (mask = cycle - 1)
+  uint32_t nassert, frame_blocks;    // nassert: the singles; frame_blocks: set by the launcher
+  uint32_t single_blocks, nstrided;  // single_blocks: set by the launcher
   const ProgStridedCells* sdesc;  // device: one per strided assertion, in stored order
   const felt* svals;     // device: the sequences' values
-  const felt* consts;    // device: the constant pool
-  const ProgPeriodic* per_desc;  // device: one per periodic column, mask = cycle - 1
-  const felt* per_tab;   // device: the periodic columns' raw values, indexed by (row & mask)
   const uint32_t* a_col; // device: assertion columns, steps and values in stored (step, column) order
   const uint32_t* a_step;
   const felt* a_val;
