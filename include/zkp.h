@@ -560,6 +560,47 @@ int zkp_build_training_update_trace(zkp_ctx* ctx, const zkp_felt* initial_state,
                                     void* d_trace_out, zkp_felt* first_last /* nullable */,
                                     zkp_felt* raw_states /* nullable */);
 
+/* The TrainingUpdate traces of all clients of a round in one call: one upload of every
+ * client's packed inputs, the K SGD chains side by side in one launch (none for bs = 0),
+ * one launch that writes the K traces, one synchronisation. A round has one shape, so bs
+ * and n are the batch's; a client carries what zkp_build_training_update_trace takes per
+ * trace, with the same meaning, and a mask source of either kind:
+ *   masks != NULL: n x 120 u64 in host memory, as the single entry's;
+ *   masks == NULL: the masks are the PCG64 stream of (pcg_state, pcg_inc), made on the
+ *     device (they are never uploaded): the mask of row t, cell c is value t * 120 + c of
+ *       s_0 = state, s_{j+1} = s_j * 0x2360ED051FC65DA44385DF649FCCF645 + inc (mod 2^128),
+ *       value e = out(s_{e+1}), out(s) = rotr64((s >> 64) ^ (s mod 2^64), s >> 122)
+ *     (zkp_pcg64_masks restates it on the host). With state and inc taken from
+ *     numpy.random.default_rng(seed).bit_generator.state["state"], these are the bits of
+ *     default_rng(seed).integers(0, 2**64, (n, 120), dtype=uint64). Halves: [0] = the low
+ *     64 bits, [1] = the high.
+ * Refusals are decided on the host before anything is uploaded or launched, leave the
+ * context usable and name the client's index in zkp_last_error: a null clients or required
+ * pointer, num_clients of 0 or above ZKP_TU_MAX_CLIENTS, a felt >= p, or two clients whose
+ * 240 * n * 16-byte output ranges overlap are ZKP_ERR_ARGUMENT; n and bs follow the single
+ * entry's ZKP_ERR_TRACE_SHAPE rules. */
+#define ZKP_TU_MAX_CLIENTS 64
+typedef struct zkp_training_client {
+  const zkp_felt* initial_state;         /* 120 felts */
+  const zkp_felt* x_batch;               /* bs x 9 (unused when bs = 0, as x_sign and y_batch) */
+  const zkp_felt* x_sign;                /* bs x 9 */
+  const zkp_felt* y_batch;               /* bs x 6 */
+  zkp_felt learning_rate, precision;
+  const uint64_t* masks;                 /* n x 120 host u64, or NULL: pcg_state, pcg_inc */
+  uint64_t pcg_state[2], pcg_inc[2];     /* lo, hi; read only when masks is NULL */
+  void* d_trace_out;                     /* device: 240 * n * 16 bytes */
+  zkp_felt* first_last;                  /* nullable, 240 felts */
+  zkp_felt* raw_states;                  /* nullable, (bs + 1) x 120 felts */
+} zkp_training_client;
+int zkp_build_training_update_traces(zkp_ctx* ctx, const zkp_training_client* clients, uint32_t num_clients,
+                                     uint64_t bs, uint64_t n);
+
+/* Values [first_index, first_index + count) of the PCG64 stream of (state, inc) defined
+ * above, into out (host only, no context): what the device writes as masks, restated for
+ * a fork and for CPU checks. Halves are lo, hi. ZKP_ERR_ARGUMENT for a null pointer. */
+int zkp_pcg64_masks(const uint64_t state[2], const uint64_t inc[2], uint64_t first_index, uint64_t count,
+                    uint64_t* out);
+
 /* ---- profiling ------------------------------------------------------- */
 /* When enabled, every kernel launch is bracketed with HIP events on the
  * stream it runs on; zkp_kernel_stats reports per-kernel launch count and

@@ -86,7 +86,7 @@ EXPORTED = [
     "zkp_comm_rccl_create", "zkp_comm_destroy", "zkp_comm_rank", "zkp_comm_world", "zkp_comm_backend_world", "zkp_comm_check",
     "zkp_prove_sharded_device",
     "zkp_verify", "zkp_build_global_update_trace", "zkp_set_profiling_kernel",
-    "zkp_build_training_update_trace",
+    "zkp_build_training_update_trace", "zkp_build_training_update_traces", "zkp_pcg64_masks",
     "zkp_session_create", "zkp_session_destroy", "zkp_session_trace_lde", "zkp_eval_constraints",
     "zkp_composition_commit", "zkp_ood_frame", "zkp_deep_fri", "zkp_query", "zkp_comm_host_create",
     "zkp_session_shape",
@@ -155,6 +155,39 @@ class AirProgramC(ctypes.Structure):
     ]
 
 
+TU_MAX_CLIENTS = 64  # ZKP_TU_MAX_CLIENTS (include/zkp.h)
+
+
+class TrainingClientC(ctypes.Structure):
+    """`zkp_training_client` (include/zkp.h)."""
+    _fields_ = [
+        ("initial_state", ctypes.c_void_p), ("x_batch", ctypes.c_void_p), ("x_sign", ctypes.c_void_p),
+        ("y_batch", ctypes.c_void_p), ("learning_rate", Felt), ("precision", Felt),
+        ("masks", ctypes.c_void_p), ("pcg_state", ctypes.c_uint64 * 2), ("pcg_inc", ctypes.c_uint64 * 2),
+        ("d_trace_out", ctypes.c_void_p), ("first_last", ctypes.c_void_p), ("raw_states", ctypes.c_void_p),
+    ]
+
+
+def pcg64_state(seed: int):
+    """(state, inc) of np.random.default_rng(seed)'s PCG64, as Python ints: the stream whose
+    raw output default_rng(seed).integers(0, 2**64, ..., dtype=uint64) returns."""
+    st = np.random.default_rng(seed).bit_generator.state
+    if st["bit_generator"] != "PCG64" or st["has_uint32"]:
+        raise RuntimeError("numpy's default_rng is not a fresh PCG64")
+    return int(st["state"]["state"]), int(st["state"]["inc"])
+
+
+def pcg64_masks(state: int, inc: int, first_index: int, count: int) -> np.ndarray:
+    """zkp_pcg64_masks (host only): values [first_index, first_index + count) of the stream."""
+    m64 = 2**64 - 1
+    out = np.empty(count, dtype=np.uint64)
+    rc = load().zkp_pcg64_masks((ctypes.c_uint64 * 2)(state & m64, state >> 64),
+                                (ctypes.c_uint64 * 2)(inc & m64, inc >> 64), first_index, count, out.ctypes.data)
+    if rc:
+        raise ZkpError(rc, "zkp_pcg64_masks")
+    return out
+
+
 def _air(air) -> int:
     """An AIR id: a built-in id, or an object carrying one (a registered AirProgram, an Air class)."""
     return int(getattr(air, "AIR_ID", air))
@@ -221,6 +254,8 @@ def load():
         L.zkp_verify.restype = i32
         L.zkp_build_global_update_trace.argtypes = [vp, vp, vp, vp, u64, Felt, u64, vp, vp]
         L.zkp_build_training_update_trace.argtypes = [vp, vp, vp, vp, vp, u64, Felt, Felt, vp, u64, vp, vp, vp]
+        L.zkp_build_training_update_traces.argtypes = [vp, ctypes.POINTER(TrainingClientC), u32, u64, u64]
+        L.zkp_pcg64_masks.argtypes = [vp, vp, u64, u64, vp]
         L.zkp_comm_host_create.argtypes = [i32, i32, ctypes.POINTER(HostTransport), ctypes.POINTER(vp)]
         L.zkp_session_create.argtypes = [vp, i32, u32, u64, vp, u64, popt, ctypes.POINTER(vp)]
         L.zkp_session_destroy.argtypes = [vp]
@@ -613,6 +648,53 @@ class Context:
             raw = _ints(raw)
             return fl[:120], fl[120:], [raw[i * 120:(i + 1) * 120] for i in range(bs + 1)]
         return fl[:120], fl[120:]
+
+    def build_training_update_traces(self, clients, bs: int, n: int, want_raw_states: bool = False):
+        """zkp_build_training_update_traces: the TrainingUpdate traces (240 x n each) of all
+        clients of a round in one call. `clients` is a list of dicts with the single
+        builder's per-trace arguments: initial_state, x_batch, x_sign, y_batch (bs rows each),
+        learning_rate, precision, d_out, and a mask source: masks = an (n, 120) uint64 array
+        uploaded as it is, or pcg = (state, inc) of a PCG64 stream (pcg64_state(seed)) that
+        the device turns into the masks itself. Returns one (first, last) per client, or
+        (first, last, raw_states) with want_raw_states."""
+        mask64 = 2**64 - 1
+        flat = lambda rows: _felts([v for row in rows for v in row]) if bs else None
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        arr = (TrainingClientC * max(1, len(clients)))()
+        keep = []  # the packed arrays stay referenced until the call returns
+        for c, cl in zip(arr, clients):
+            st, x, xs, y = _felts(cl["initial_state"]), flat(cl["x_batch"]), flat(cl["x_sign"]), flat(cl["y_batch"])
+            if st.shape != (120, 2):
+                raise ValueError("initial_state must hold 120 felts")
+            if bs and (x.shape, xs.shape, y.shape) != ((bs * 9, 2), (bs * 9, 2), (bs * 6, 2)):
+                raise ValueError("x_batch, x_sign must be bs x 9 and y_batch bs x 6")
+            fl = np.zeros((240, 2), dtype=np.uint64)
+            raw = np.zeros(((bs + 1) * 120, 2), dtype=np.uint64) if want_raw_states else None
+            masks = cl.get("masks")
+            if masks is not None:
+                masks = np.ascontiguousarray(masks, dtype=np.uint64)
+                if masks.shape != (n, 120):
+                    raise ValueError("masks must be (n, 120) uint64")
+            else:
+                state, inc = cl["pcg"]
+                c.pcg_state[0], c.pcg_state[1] = state & mask64, state >> 64
+                c.pcg_inc[0], c.pcg_inc[1] = inc & mask64, inc >> 64
+            lr, pr = cl["learning_rate"], cl["precision"]
+            c.initial_state, c.x_batch, c.x_sign, c.y_batch = ptr(st), ptr(x), ptr(xs), ptr(y)
+            c.learning_rate, c.precision = Felt(lr & mask64, lr >> 64), Felt(pr & mask64, pr >> 64)
+            c.masks, c.d_trace_out, c.first_last, c.raw_states = ptr(masks), cl["d_out"], ptr(fl), ptr(raw)
+            keep.append((st, x, xs, y, masks, fl, raw))
+        rc = self.lib.zkp_build_training_update_traces(self.ptr, arr, len(clients), bs, n)
+        self._check(rc, "zkp_build_training_update_traces")
+        out = []
+        for *_, fl, raw in keep:
+            fl = _ints(fl)
+            if want_raw_states:
+                raw = _ints(raw)
+                out.append((fl[:120], fl[120:], [raw[i * 120:(i + 1) * 120] for i in range(bs + 1)]))
+            else:
+                out.append((fl[:120], fl[120:]))
+        return out
 
     def trace_lde_commit(self, trace: np.ndarray, blowup: int, want_lde: bool = True):
         trace = np.ascontiguousarray(trace, dtype=np.uint64)

@@ -114,7 +114,7 @@ def main(argv=None) -> int:
     from . import _native
     from .air import TU_STATE, GlobalUpdateAir, TrainingUpdateAir
     from .options import ProofOptions
-    from .prover import Proof, verify
+    from .prover import Proof, TrainingUpdateProver, verify
 
     opts = ProofOptions.reference()  # main.rs:98-107
     rng = random.Random(args.seed)
@@ -132,10 +132,13 @@ def main(argv=None) -> int:
     ctx = _native.Context(args.device) if args.step != "witness" else None
     step_start = time.perf_counter()
     client_reps, total_training = [], 0
-    d_trace = None  # the training traces' device allocation (one shape: reused by every device)
+    d_trace = None  # the training traces' device allocation (one shape: a slice per device)
 
     if args.step in ("setup", "proof") and args.verbose and args.step == "setup":
         print("--- Client Training Updates ---")
+    # every client's prover first (nothing else draws from rng in this loop, so the draws
+    # keep their order), then all traces in one call, then the proofs client by client
+    clients = []
     for i, dev in enumerate(devices):
         batch = _zk_batch(dev, args.bs)
         if batch is None:
@@ -149,28 +152,34 @@ def main(argv=None) -> int:
             print(f"DEBUG: Witness trace - length: {trace.length()}, width: {trace.width()}")
             client_reps.append(trace.get(0, trace.length() - 1))
             continue
-        print(f"DEBUG: {'Device' if args.step == 'setup' else 'Proof step - Device'} {i + 1}, "
-              f"batch size {args.bs}")
-        t0 = time.perf_counter()
-        # the trace is built in HBM (SGD chain and masked rows on the device) and proved there
-        width, length = 2 * TU_STATE, tp.trace_length
+        clients.append((i, tp))
+    for g in range(0, len(clients), _native.TU_MAX_CLIENTS):
+        group = clients[g:g + _native.TU_MAX_CLIENTS]
+        # the traces are built in HBM (SGD chains, masks and masked rows on the device) and proved there
+        width, length = 2 * TU_STATE, group[0][1].trace_length
         if d_trace is None:
-            d_trace = ctx.alloc(width * length * 16)
-        tp.build_trace_device(ctx, d_trace)
-        print(f"DEBUG: Trace dimensions - length: {length}, width: {width}")
-        pub = tp.get_pub_inputs()
-        proof = Proof(*ctx.prove_device(TrainingUpdateAir.AIR_ID, d_trace, width, length, pub.to_elements(), opts))
-        size = len(proof.to_bytes())
-        total_training += size
-        if args.verbose and args.step == "setup":
-            print(f"Device {i + 1:>2}: ZK proof for {args.bs} samples: gen = {_ms(t0):>4}ms, size = {size} bytes")
-            print(f"Training proof size: {size} bytes")
-        try:
-            verify(TrainingUpdateAir, proof, pub, opts)
-        except _native.VerifierError as e:
-            print(f"training proof failed!: {e}", file=sys.stderr)
-            return 101
-        client_reps.append(pub.final_masked[0])
+            d_trace = ctx.alloc(len(group) * width * length * 16)
+        t0 = time.perf_counter()
+        ptrs = TrainingUpdateProver.build_traces_device([tp for _, tp in group], ctx, d_trace)
+        build_share = (time.perf_counter() - t0) / len(group)  # of each device's proof generation time
+        for (i, tp), d in zip(group, ptrs):
+            print(f"DEBUG: {'Device' if args.step == 'setup' else 'Proof step - Device'} {i + 1}, "
+                  f"batch size {args.bs}")
+            t0 = time.perf_counter() - build_share
+            print(f"DEBUG: Trace dimensions - length: {length}, width: {width}")
+            pub = tp.get_pub_inputs()
+            proof = Proof(*ctx.prove_device(TrainingUpdateAir.AIR_ID, d, width, length, pub.to_elements(), opts))
+            size = len(proof.to_bytes())
+            total_training += size
+            if args.verbose and args.step == "setup":
+                print(f"Device {i + 1:>2}: ZK proof for {args.bs} samples: gen = {_ms(t0):>4}ms, size = {size} bytes")
+                print(f"Training proof size: {size} bytes")
+            try:
+                verify(TrainingUpdateAir, proof, pub, opts)
+            except _native.VerifierError as e:
+                print(f"training proof failed!: {e}", file=sys.stderr)
+                return 101
+            client_reps.append(pub.final_masked[0])
     if d_trace is not None:
         ctx.free(d_trace)
 

@@ -25,6 +25,107 @@ bool device_is_gfx950(int device) {
 
 // a TrainingUpdate state: 60 cells of a (value, sign) pair, half the trace's width
 constexpr uint32_t TU_STATE = TU_W / 2;
+
+// zkp_build_training_update_traces, and zkp_build_training_update_trace as its batch of
+// one. Every refusal comes before the first upload and names the client in zkp_last_error.
+int tu_build(zkp_ctx* ctx, const zkp_training_client* cl, uint32_t K, uint64_t bs, uint64_t n) {
+  HIP_CHECK(hipSetDevice(ctx->device));
+  ctx->err.clear();
+  auto refuse = [&](int code, uint32_t k, const char* what) {
+    ctx->err = "client " + std::to_string(k) + ": " + what;
+    return code;
+  };
+  for (uint32_t k = 0; k < K; k++)
+    if (!cl[k].initial_state || !cl[k].d_trace_out || (bs && (!cl[k].x_batch || !cl[k].x_sign || !cl[k].y_batch)))
+      return refuse(ZKP_ERR_ARGUMENT, k, "null initial_state, d_trace_out or batch pointer");
+  if (n < 16 || (n & (n - 1)) || n <= bs || n > (1ull << MAX_LOG_TRACE)) return (int)ZKP_ERR_TRACE_SHAPE;
+  auto canon = [](const zkp_felt* v, uint64_t cnt) {
+    for (uint64_t i = 0; i < cnt; i++)
+      if (ge_p(make(v[i].lo, v[i].hi))) return false;
+    return true;
+  };
+  for (uint32_t k = 0; k < K; k++)
+    if (ge_p(make(cl[k].learning_rate.lo, cl[k].learning_rate.hi)) ||
+        ge_p(make(cl[k].precision.lo, cl[k].precision.hi)) || !canon(cl[k].initial_state, TU_STATE) ||
+        !canon(cl[k].x_batch, bs * TU_FE) || !canon(cl[k].x_sign, bs * TU_FE) || !canon(cl[k].y_batch, bs * TU_AC))
+      return refuse(ZKP_ERR_ARGUMENT, k, "a felt >= p");
+  const uint64_t out_bytes = (uint64_t)TU_W * n * 16;
+  std::vector<std::pair<uintptr_t, uint32_t>> outs(K);
+  for (uint32_t k = 0; k < K; k++) outs[k] = {(uintptr_t)cl[k].d_trace_out, k};
+  std::sort(outs.begin(), outs.end());
+  for (uint32_t i = 1; i < K; i++)
+    if (outs[i].first - outs[i - 1].first < out_bytes)
+      return refuse(ZKP_ERR_ARGUMENT, std::max(outs[i].second, outs[i - 1].second),
+                    "d_trace_out overlaps another client's trace");
+
+  // one packed upload: [descriptors | initial states (K x 120) | batches (K x bs x 24)]
+  const uint64_t batch_felts = bs * (2 * TU_FE + TU_AC);
+  const size_t off_init = (size_t)K * sizeof(TuClient), off_batch = off_init + (size_t)K * TU_STATE * 16;
+  const size_t packed_bytes = off_batch + (size_t)K * batch_felts * 16;
+  uint64_t mask_clients = 0;
+  for (uint32_t k = 0; k < K; k++) mask_clients += cl[k].masks != nullptr;
+  uint64_t* dm = ctx->buf<uint64_t>("tu_masks", mask_clients * n * TU_STATE);
+  uint8_t* dp = ctx->buf<uint8_t>("tu_packed", packed_bytes);
+  felt* ds = ctx->buf<felt>("tu_states", (size_t)K * (bs + 1) * TU_STATE);
+  felt* dfl = ctx->buf<felt>("tu_first_last", (size_t)K * 2 * TU_STATE);
+  std::vector<uint8_t> packed(packed_bytes);
+  uint64_t mi = 0;
+  for (uint32_t k = 0; k < K; k++) {
+    const zkp_training_client& c = cl[k];
+    TuClient d{};
+    d.out = (felt*)c.d_trace_out;
+    // divisors of signed.rs div_generic (0 is accepted: winterfell inv(0) = 0)
+    d.pr_inv = inv(make(c.precision.lo, c.precision.hi));
+    d.lr_inv = inv(make(c.learning_rate.lo, c.learning_rate.hi));
+    if (c.masks) {
+      d.masks = dm + mi++ * n * TU_STATE;
+    } else {
+      d.pcg_state = {c.pcg_state[0], c.pcg_state[1]};
+      pcg::doubled_pairs({c.pcg_inc[0], c.pcg_inc[1]}, pcg::JUMP_BITS, d.pcg_mul, d.pcg_inc);
+    }
+    memcpy(packed.data() + k * sizeof(TuClient), &d, sizeof d);
+    memcpy(packed.data() + off_init + (size_t)k * TU_STATE * 16, c.initial_state, TU_STATE * 16);
+    if (bs) {
+      uint8_t* b = packed.data() + off_batch + (size_t)k * batch_felts * 16;  // [x | x_sign | y]
+      memcpy(b, c.x_batch, bs * TU_FE * 16);
+      memcpy(b + bs * TU_FE * 16, c.x_sign, bs * TU_FE * 16);
+      memcpy(b + 2 * bs * TU_FE * 16, c.y_batch, bs * TU_AC * 16);
+    }
+  }
+  ctx->upload(dp, packed.data(), packed_bytes);
+  mi = 0;
+  for (uint32_t k = 0; k < K; k++)
+    if (cl[k].masks) ctx->upload(dm + mi++ * n * TU_STATE, cl[k].masks, n * TU_STATE * 8);
+  const TuClient* dcl = (const TuClient*)dp;
+  const felt* dinit = (const felt*)(dp + off_init);
+  // the unmasked states: rows 1..bs by the chain kernel, which also writes row 0; without
+  // samples a client's states are its initial state, where it was uploaded
+  if (bs)  // mse_prime divides by f64_to_felt(6.0) (helper.rs:245-269)
+    launch_tu_states(ctx->prof, ctx->stream, dcl, K, dinit, (const felt*)(dp + off_batch), ds, (uint32_t)bs,
+                     inv(felt_u64(TU_AC * 1000000ull)));
+  const felt* states = bs ? ds : dinit;
+  launch_tu_write(ctx->prof, ctx->stream, dcl, K, states, bs, n, dfl);
+  // what the clients asked back: copied into one pinned block, one synchronisation
+  bool want_fl = false, want_raw = false;
+  for (uint32_t k = 0; k < K; k++) {
+    want_fl |= cl[k].first_last != nullptr;
+    want_raw |= cl[k].raw_states != nullptr;
+  }
+  const size_t fl_bytes = (size_t)K * 2 * TU_STATE * 16, raw_bytes = (size_t)K * (bs + 1) * TU_STATE * 16;
+  uint8_t* hp = (uint8_t*)ctx->pinned((want_fl ? fl_bytes : 0) + (want_raw ? raw_bytes : 0));
+  uint8_t* hraw = hp + (want_fl ? fl_bytes : 0);
+  if (want_fl) HIP_CHECK(hipMemcpyAsync(hp, dfl, fl_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (want_raw) HIP_CHECK(hipMemcpyAsync(hraw, states, raw_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  ctx->sync();
+  for (uint32_t k = 0; k < K; k++) {
+    if (cl[k].first_last) memcpy(cl[k].first_last, hp + (size_t)k * 2 * TU_STATE * 16, 2 * TU_STATE * 16);
+    if (cl[k].raw_states)
+      memcpy(cl[k].raw_states, hraw + (size_t)k * (bs + 1) * TU_STATE * 16, (bs + 1) * TU_STATE * 16);
+  }
+  ctx->collect_prof();
+  ctx->free_retired();  // buffers a larger batch or trace outgrew (no proof's finish follows)
+  return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -260,46 +361,49 @@ int zkp_build_training_update_trace(zkp_ctx* ctx, const zkp_felt* initial_state,
                                     zkp_felt learning_rate, zkp_felt precision, const uint64_t* masks, uint64_t n,
                                     void* d_trace_out, zkp_felt* first_last, zkp_felt* raw_states) {
   return guarded(ctx, [&] {
-    HIP_CHECK(hipSetDevice(ctx->device));
-    if (!initial_state || !masks || !d_trace_out || (bs && (!x_batch || !x_sign || !y_batch)))
-      return (int)ZKP_ERR_ARGUMENT;
-    if (n < 16 || (n & (n - 1)) || n <= bs || n > (1ull << MAX_LOG_TRACE)) return (int)ZKP_ERR_TRACE_SHAPE;
-    const felt lr = make(learning_rate.lo, learning_rate.hi), pr = make(precision.lo, precision.hi);
-    auto canon = [](const zkp_felt* v, uint64_t cnt) {
-      for (uint64_t i = 0; i < cnt; i++)
-        if (ge_p(make(v[i].lo, v[i].hi))) return false;
-      return true;
-    };
-    if (ge_p(lr) || ge_p(pr) || !canon(initial_state, TU_STATE) || !canon(x_batch, bs * TU_FE) ||
-        !canon(x_sign, bs * TU_FE) || !canon(y_batch, bs * TU_AC))
-      return (int)ZKP_ERR_ARGUMENT;
-    // the unmasked states: row 0 uploaded, rows 1..bs by the chain kernel (none for bs = 0)
-    felt* ds = ctx->buf<felt>("tu_states", (bs + 1) * TU_STATE);
-    ctx->upload(ds, initial_state, TU_STATE * 16);
-    if (bs) {
-      std::vector<zkp_felt> in;  // [x | x_sign | y]
-      in.reserve(bs * (2 * TU_FE + TU_AC));
-      in.insert(in.end(), x_batch, x_batch + bs * TU_FE);
-      in.insert(in.end(), x_sign, x_sign + bs * TU_FE);
-      in.insert(in.end(), y_batch, y_batch + bs * TU_AC);
-      felt* din = ctx->buf<felt>("tu_batch", in.size());
-      ctx->upload(din, in.data(), in.size() * 16);
-      // divisors of signed.rs div_generic (0 is accepted: winterfell inv(0) = 0); mse_prime
-      // divides by f64_to_felt(6.0) (helper.rs:245-269)
-      launch_tu_states(ctx->prof, ctx->stream, ds, din, din + bs * TU_FE, din + 2 * bs * TU_FE, (uint32_t)bs,
-                       inv(pr), inv(lr), inv(felt_u64(TU_AC * 1000000ull)));
-    }
-    uint64_t* dm = ctx->buf<uint64_t>("tu_masks", n * TU_STATE);
-    ctx->upload(dm, masks, n * TU_STATE * 8);
-    felt* dfl = ctx->buf<felt>("tu_first_last", 2 * TU_STATE);
-    launch_tu_write(ctx->prof, ctx->stream, dm, ds, bs, n, (felt*)d_trace_out, dfl);
-    if (first_last) ctx->download(first_last, dfl, 2 * TU_STATE * 16);
-    if (raw_states) ctx->download(raw_states, ds, (bs + 1) * TU_STATE * 16);
-    ctx->sync();
-    ctx->collect_prof();
-    ctx->free_retired();  // buffers a larger batch or trace outgrew (no proof's finish follows)
-    return 0;
+    if (!masks) return (int)ZKP_ERR_ARGUMENT;  // this entry takes host masks only
+    zkp_training_client c{};
+    c.initial_state = initial_state;
+    c.x_batch = x_batch;
+    c.x_sign = x_sign;
+    c.y_batch = y_batch;
+    c.learning_rate = learning_rate;
+    c.precision = precision;
+    c.masks = masks;
+    c.d_trace_out = d_trace_out;
+    c.first_last = first_last;
+    c.raw_states = raw_states;
+    return tu_build(ctx, &c, 1, bs, n);
   });
+}
+
+int zkp_build_training_update_traces(zkp_ctx* ctx, const zkp_training_client* clients, uint32_t num_clients,
+                                     uint64_t bs, uint64_t n) {
+  return guarded(ctx, [&] {
+    if (!clients || num_clients == 0 || num_clients > ZKP_TU_MAX_CLIENTS) {
+      ctx->err = "clients must be non-null and 1.." + std::to_string(ZKP_TU_MAX_CLIENTS) + " in number";
+      return (int)ZKP_ERR_ARGUMENT;
+    }
+    return tu_build(ctx, clients, num_clients, bs, n);
+  });
+}
+
+int zkp_pcg64_masks(const uint64_t state[2], const uint64_t inc[2], uint64_t first_index, uint64_t count,
+                    uint64_t* out) {
+  if (!state || !inc || (count && !out)) return ZKP_ERR_ARGUMENT;
+  // s_first_index by square-and-multiply over the doubled pairs, made as they are needed
+  pcg::u128 s{state[0], state[1]}, a{pcg::MUL_LO, pcg::MUL_HI}, c{inc[0], inc[1]};
+  const pcg::u128 step_a = a, step_c = c;
+  for (uint64_t k = first_index; k; k >>= 1) {
+    if (k & 1) s = pcg::affine(s, a, c);
+    c = pcg::mul(c, pcg::add(a, {1, 0}));
+    a = pcg::mul(a, a);
+  }
+  for (uint64_t i = 0; i < count; i++) {
+    s = pcg::affine(s, step_a, step_c);
+    out[i] = pcg::out(s);
+  }
+  return ZKP_OK;
 }
 
 int zkp_set_profiling(zkp_ctx* ctx, int enabled) {

@@ -1195,18 +1195,27 @@ __device__ __forceinline__ sfelt tu_scale(sfelt a, felt k) {
   return {tu_blend(a.s, tu_wrap(q), q), a.s};
 }
 
-// states[0] = the initial state; states[k + 1] = the state after sample k. One wave:
-// thread c < 60 owns cell c. x, xs: bs x 9, y: bs x 6; pr_inv, lr_inv, ac_inv = the
-// inverses of the precision, the learning rate and f64_to_felt(6.0). The steps are
-// serial and one wave's field products run one after the other, so a step's time is
-// its chain of products: cleansed values are kept beside the values they belong to,
-// and the next sample's features are fetched by threads that idle during the fold.
-__global__ __launch_bounds__(64) void k_tu_states(felt* __restrict__ states, const felt* __restrict__ x,
-                                                  const felt* __restrict__ xs, const felt* __restrict__ y,
-                                                  uint32_t bs, felt pr_inv, felt lr_inv, felt ac_inv) {
+// One workgroup of one wave per client (blockIdx.x; the chains of a round are independent
+// and each is latency-bound, so K of them take one chain's time). Of its client:
+// states[0] = the initial state; states[k + 1] = the state after sample k. Thread c < 60
+// owns cell c. batch = [x (bs x 9) | xs (bs x 9) | y (bs x 6)]; pr_inv, lr_inv (the
+// client's descriptor), ac_inv = the inverses of the precision, the learning rate and
+// f64_to_felt(6.0). The steps are serial and one wave's field products run one after the
+// other, so a step's time is its chain of products: cleansed values are kept beside the
+// values they belong to, and the next sample's features are fetched by threads that idle
+// during the fold.
+__global__ __launch_bounds__(64) void k_tu_states(const TuClient* __restrict__ clients,
+                                                  const felt* __restrict__ initial, const felt* __restrict__ batch,
+                                                  felt* __restrict__ all_states, uint32_t bs, felt ac_inv) {
   // state (value, sign, cleansed), forward products, errors, features (two samples)
   __shared__ felt sv[TU_CELLS], ss[TU_CELLS], sc[TU_CELLS], pv[TU_WC], ps[TU_WC], pc[TU_WC], ev[TU_AC], es[TU_AC],
       xsg[2][TU_FE], xc[2][TU_FE];
+  const uint32_t client = blockIdx.x;
+  const felt pr_inv = clients[client].pr_inv, lr_inv = clients[client].lr_inv;
+  const felt* x = batch + (uint64_t)client * bs * (2 * TU_FE + TU_AC);
+  const felt* xs = x + (uint64_t)bs * TU_FE;
+  const felt* y = xs + (uint64_t)bs * TU_FE;
+  felt* states = all_states + (uint64_t)client * (bs + 1) * TU_HALF;
   const uint32_t c = threadIdx.x;
   const bool cell = c < TU_CELLS, wcell = c < TU_WC;
   const uint32_t i = wcell ? c / TU_FE : c - TU_WC, j = c % TU_FE;  // w[i][j] or b[i]
@@ -1217,7 +1226,9 @@ __global__ __launch_bounds__(64) void k_tu_states(felt* __restrict__ states, con
     xc[k & 1][c - TU_AC] = tu_cleanse(f);
   };
   if (cell) {
-    const sfelt own{states[2 * c], states[2 * c + 1]};
+    const sfelt own{initial[client * TU_HALF + 2 * c], initial[client * TU_HALF + 2 * c + 1]};
+    states[2 * c] = own.v;
+    states[2 * c + 1] = own.s;
     sv[c] = own.v;
     ss[c] = own.s;
     sc[c] = tu_cleanse(own);
@@ -1275,17 +1286,40 @@ __global__ __launch_bounds__(64) void k_tu_states(felt* __restrict__ states, con
 // masks goes through LDS, read from HBM as one contiguous run and written as runs of
 // TU_ROWS consecutive rows per column. The odd pitch (121 x 8 B) puts the TU_ROWS rows
 // of a column in distinct LDS banks. The tile is 30976 B. first_last = the masked
-// columns of row 0, then of row n - 1.
-constexpr uint32_t TU_ROWS = 32, TU_PITCH = TU_HALF + 1;
+// columns of row 0, then of row n - 1. blockIdx.y = the client. A client without masks
+// in HBM fills the tile from its PCG64 stream (pcg64.hpp) instead: the tile is the
+// TU_ROWS * 120 consecutive values from index t0 * 120, thread i makes the TU_RUN of them
+// from t0 * 120 + i * TU_RUN, jumping once to the state before its first (the doubled
+// pairs: uniform reads of the descriptor) and stepping from there, so those masks exist
+// in HBM only as the trace's columns 120..239.
+constexpr uint32_t TU_ROWS = 32, TU_PITCH = TU_HALF + 1, TU_RUN = TU_ROWS * TU_HALF / TPB;
+static_assert(TU_RUN * TPB == TU_ROWS * TU_HALF, "a tile is TPB runs of TU_RUN values");
 
-__global__ __launch_bounds__(TPB) void k_tu_write(const uint64_t* __restrict__ masks,
-                                                  const felt* __restrict__ states, uint64_t bs, uint64_t n,
-                                                  felt* __restrict__ out, felt* __restrict__ first_last) {
+__global__ __launch_bounds__(TPB) void k_tu_write(const TuClient* __restrict__ clients,
+                                                  const felt* __restrict__ all_states, uint64_t bs, uint64_t n,
+                                                  felt* __restrict__ all_first_last) {
   __shared__ uint64_t tile[TU_ROWS * TU_PITCH];
+  const TuClient& cl = clients[blockIdx.y];
+  const felt* states = all_states + (uint64_t)blockIdx.y * (bs + 1) * TU_HALF;
+  felt* out = cl.out;
+  felt* first_last = all_first_last + (uint64_t)blockIdx.y * 2 * TU_HALF;
   const uint64_t t0 = (uint64_t)blockIdx.x * TU_ROWS;
   const uint32_t rows = n - t0 < TU_ROWS ? (uint32_t)(n - t0) : TU_ROWS;
-  const uint64_t* src = masks + t0 * TU_HALF;
-  for (uint32_t e = threadIdx.x; e < rows * TU_HALF; e += TPB) tile[e / TU_HALF * TU_PITCH + e % TU_HALF] = src[e];
+  if (cl.masks) {
+    const uint64_t* src = cl.masks + t0 * TU_HALF;
+    for (uint32_t e = threadIdx.x; e < rows * TU_HALF; e += TPB) tile[e / TU_HALF * TU_PITCH + e % TU_HALF] = src[e];
+  } else {
+    const uint32_t e0 = threadIdx.x * TU_RUN;
+    if (e0 < rows * TU_HALF) {  // rows * 120 is a multiple of TU_RUN for the even row counts n allows
+      // n <= 2^MAX_LOG_TRACE: the index is below 2^JUMP_BITS
+      pcg::u128 s = pcg::jump(cl.pcg_state, cl.pcg_mul, cl.pcg_inc, (uint32_t)(t0 * TU_HALF) + e0);
+#pragma unroll
+      for (uint32_t e = e0; e < e0 + TU_RUN; e++) {
+        s = pcg::affine(s, cl.pcg_mul[0], cl.pcg_inc[0]);
+        tile[e / TU_HALF * TU_PITCH + e % TU_HALF] = pcg::out(s);
+      }
+    }
+  }
   __syncthreads();
   const uint32_t r = threadIdx.x % TU_ROWS;
   if (r >= rows) return;
@@ -1771,17 +1805,18 @@ void launch_gu_trace(Prof& prof, hipStream_t s, const felt* masked, const felt* 
                             kinv, n, tile_buf, out));
 }
 
-void launch_tu_states(Prof& prof, hipStream_t s, felt* states, const felt* x, const felt* xs, const felt* y,
-                      uint32_t bs, felt pr_inv, felt lr_inv, felt ac_inv) {
-  LAUNCH(prof, "tu_states", s, (double)bs * (2 * TU_FE + TU_AC + TU_HALF) * 16.0,
-         hipLaunchKernelGGL(k_tu_states, dim3(1), dim3(64), 0, s, states, x, xs, y, bs, pr_inv, lr_inv, ac_inv));
+void launch_tu_states(Prof& prof, hipStream_t s, const TuClient* clients, uint32_t K, const felt* initial,
+                      const felt* batch, felt* states, uint32_t bs, felt ac_inv) {
+  LAUNCH(prof, "tu_states", s, (double)K * bs * (2 * TU_FE + TU_AC + TU_HALF) * 16.0,
+         hipLaunchKernelGGL(k_tu_states, dim3(K), dim3(64), 0, s, clients, initial, batch, states, bs, ac_inv));
 }
 
-void launch_tu_write(Prof& prof, hipStream_t s, const uint64_t* masks, const felt* states, uint64_t bs, uint64_t n,
-                     felt* out, felt* first_last) {
-  LAUNCH(prof, "tu_trace", s, (double)n * TU_HALF * (8.0 + 32.0),
-         hipLaunchKernelGGL(k_tu_write, dim3((uint32_t)((n + TU_ROWS - 1) / TU_ROWS)), dim3(TPB), 0, s, masks,
-                            states, bs, n, out, first_last));
+void launch_tu_write(Prof& prof, hipStream_t s, const TuClient* clients, uint32_t K, const felt* states,
+                     uint64_t bs, uint64_t n, felt* first_last) {
+  // the masks' 8 bytes per cell are read only by the clients that hold theirs in HBM: counted for all
+  LAUNCH(prof, "tu_trace", s, (double)K * n * TU_HALF * (8.0 + 32.0),
+         hipLaunchKernelGGL(k_tu_write, dim3((uint32_t)((n + TU_ROWS - 1) / TU_ROWS), K), dim3(TPB), 0, s, clients,
+                            states, bs, n, first_last));
 }
 
 void launch_dt_eval_consts(Prof& prof, hipStream_t s, int air, const felt* cc, felt k, felt w_last, const felt* aval,

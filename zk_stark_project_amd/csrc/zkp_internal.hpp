@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "felt.hpp"
+#include "pcg64.hpp"
 
 // ---------------------------------------------------------------- profiling
 // Every launch goes through Prof::begin/end; when enabled each launch is
@@ -207,17 +208,25 @@ void launch_dt_draw_z(Prof& prof, hipStream_t s, uint32_t* seed, const uint32_t*
 // 60 * ceil(n / 4096) felts
 void launch_gu_trace(Prof& prof, hipStream_t s, const felt* masked, const felt* raw, const felt* local,
                      uint64_t ndev, felt kinv, uint64_t n, felt* tile_buf, felt* out);
-// TrainingUpdate trace (src/training/prover.rs:90-218). states: (bs + 1) x 120 felts
-// with row 0 = the initial state ([v, s] pairs, w row-major then b); launch_tu_states
-// fills rows 1..bs with the signed fixed-point SGD steps over x, xs (bs x 9) and y
-// (bs x 6), given the inverses of the precision, the learning rate and
-// f64_to_felt(6.0). launch_tu_write: row t of the 240 x n column-major trace =
-// [states[min(t, bs)] + masks[t] | masks[t]] from n x 120 row-major u64 masks;
-// first_last (240 felts) = the masked half of row 0, then of row n - 1
-void launch_tu_states(Prof& prof, hipStream_t s, felt* states, const felt* x, const felt* xs, const felt* y,
-                      uint32_t bs, felt pr_inv, felt lr_inv, felt ac_inv);
-void launch_tu_write(Prof& prof, hipStream_t s, const uint64_t* masks, const felt* states, uint64_t bs, uint64_t n,
-                     felt* out, felt* first_last);
+// TrainingUpdate traces of the K clients of a round (src/training/prover.rs:90-218), one
+// shape (bs, n) for all. Client k's descriptor, read by the kernels through uniform loads:
+struct TuClient {
+  felt* out;              // its 240 x n column-major trace
+  const uint64_t* masks;  // device: n x 120 row-major u64 masks, or null: the PCG64 stream below
+  felt pr_inv, lr_inv;    // the inverses of its precision and learning rate
+  pcg::u128 pcg_state;    // s_0 of the stream (pcg64.hpp): the mask of row t, cell c is value t * 120 + c
+  pcg::u128 pcg_mul[pcg::JUMP_BITS], pcg_inc[pcg::JUMP_BITS];  // its doubled pairs
+};
+// states: K x (bs + 1) x 120 felts. launch_tu_states (bs > 0), one workgroup per client:
+// row 0 = initial[k] (120 felts: [v, s] pairs, w row-major then b), rows 1..bs = the
+// signed fixed-point SGD steps over batch[k] = [x (bs x 9) | x signs (bs x 9) | y (bs x 6)],
+// ac_inv = the inverse of f64_to_felt(6.0). launch_tu_write: row t of client k's trace =
+// [states[k][min(t, bs)] + mask_t | mask_t]; first_last (K x 240 felts) = the masked half
+// of its row 0, then of its row n - 1
+void launch_tu_states(Prof& prof, hipStream_t s, const TuClient* clients, uint32_t K, const felt* initial,
+                      const felt* batch, felt* states, uint32_t bs, felt ac_inv);
+void launch_tu_write(Prof& prof, hipStream_t s, const TuClient* clients, uint32_t K, const felt* states,
+                     uint64_t bs, uint64_t n, felt* first_last);
 
 // ---------------------------------------------------------------- constraints
 // Points of a coset-major shard: local index q = c*n + t is cx[c] * w_n^t,

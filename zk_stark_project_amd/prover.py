@@ -284,12 +284,7 @@ class TrainingUpdateProver(Prover):
         rows for get_pub_inputs(). The masks are build_trace()'s: the same trace."""
         ctx = ctx or self.context()
         n, half = self.trace_length, TU_STATE
-        initial = []
-        for row, srow in zip(self.initial_w, self.w_sign):
-            for v, s in zip(row, srow):
-                initial += [v % P, s % P]
-        for v, s in zip(self.initial_b, self.b_sign):
-            initial += [v % P, s % P]
+        initial = self._initial_state()
         rng = np.random.default_rng(self.mask_seed)
         masks = rng.integers(0, 1 << 64, size=(n, half), dtype=np.uint64, endpoint=False)
         d = d_out if d_out is not None else ctx.alloc(2 * half * n * 16)
@@ -302,6 +297,58 @@ class TrainingUpdateProver(Prover):
                 ctx.free(d)
             raise
         return d
+
+    def _initial_state(self):
+        """Row 0 before masking: [v, s] pairs, w row-major then b (prover.rs:98-103)."""
+        initial = []
+        for row, srow in zip(self.initial_w, self.w_sign):
+            for v, s in zip(row, srow):
+                initial += [v % P, s % P]
+        for v, s in zip(self.initial_b, self.b_sign):
+            initial += [v % P, s % P]
+        return initial
+
+    @staticmethod
+    def build_traces_device(provers, ctx=None, d_out=None, device_masks=True):
+        """build_trace_device() for all clients of a round in one call
+        (zkp_build_training_update_traces: the clients' SGD chains run side by side and one
+        launch writes every trace). The provers share one trace_length and batch_size
+        (ValueError otherwise). Returns one device pointer per prover, slices of one
+        allocation of len(provers) * 240 * n * 16 bytes (d_out, or a new one whose first
+        pointer the caller frees with ctx.free), and keeps each prover's first and last
+        masked rows for its get_pub_inputs(). device_masks=True: the device makes each
+        prover's masks from its mask_seed (numpy's PCG64 stream, the same bits as
+        build_trace()'s draw, never drawn or uploaded by the host); False: numpy's draw goes
+        through the same call. The traces are build_trace()'s either way."""
+        provers = list(provers)
+        if not provers:
+            return []
+        n, bs, half = provers[0].trace_length, provers[0].batch_size, TU_STATE
+        if any(p.trace_length != n or p.batch_size != bs for p in provers):
+            raise ValueError("the provers of a batch share one trace_length and one batch_size")
+        ctx = ctx or provers[0].context()
+        stride = 2 * half * n * 16
+        base = d_out if d_out is not None else ctx.alloc(len(provers) * stride)
+        ptrs = [base + i * stride for i in range(len(provers))]
+        clients = []
+        for p, d in zip(provers, ptrs):
+            cl = dict(initial_state=p._initial_state(), x_batch=p.x_batch, x_sign=p.x_batch_sign, y_batch=p.y_batch,
+                      learning_rate=p.learning_rate, precision=p.precision, d_out=d)
+            if device_masks:
+                cl["pcg"] = _native.pcg64_state(p.mask_seed)
+            else:
+                cl["masks"] = np.random.default_rng(p.mask_seed).integers(0, 1 << 64, size=(n, half), dtype=np.uint64,
+                                                                          endpoint=False)
+            clients.append(cl)
+        try:
+            rows = ctx.build_training_update_traces(clients, bs, n)
+        except Exception:
+            if d_out is None:
+                ctx.free(base)
+            raise
+        for p, fl in zip(provers, rows):
+            p._first_last = fl
+        return ptrs
 
     def get_pub_inputs(self, trace: TraceTable | None = None) -> TrainingUpdateInputs:
         """prover.rs:236-270 (without a trace: the rows that build_trace_device() kept)."""
