@@ -60,11 +60,13 @@ typedef enum zkp_air_id {
  * A zkp_air_program states an AIR as data: the transition constraints as a
  * straight-line program of field operations that the device runs at every point
  * of the constraint-evaluation domain (and the host verifier at the OOD point),
- * periodic columns, and single-row assertions. Its values are concrete for one
- * instance: constants, assertion steps and assertion values are what `Air::new`
- * derives from the public inputs. zkp_air_register returns an id (>= 16) that
- * every entry point taking a zkp_air_id accepts; `pub_elems` still seeds the
- * coin there, the program itself never reads it.
+ * periodic columns, and single-row assertions. Registered through zkp_air_register
+ * or zkp_air_register_strided its values are concrete for one instance: constants,
+ * assertion steps and assertion values are what `Air::new` derives from the public
+ * inputs, `pub_elems` still seeds the coin, and the program itself never reads it.
+ * zkp_air_register_params (below) registers one program for every instance: its
+ * operands and assertion values may come from each proof's `pub_elems`. Each entry
+ * returns an id (>= 16) that every entry point taking a zkp_air_id accepts.
  *
  * Op encoding (one uint64_t per op):
  *   bits  0..7   opcode (ZKP_OP_*)
@@ -74,7 +76,8 @@ typedef enum zkp_air_id {
  *   bits 48..63  zero
  * An operand is (kind << 13) | index with kind one of ZKP_SRC_*:
  *   REG index < num_registers, CUR / NEXT index < width (the frame's two rows),
- *   PERIODIC index < num_periodic, CONST index < num_constants.
+ *   PERIODIC index < num_periodic, CONST index < num_constants, PUB (zkp_air_register_params
+ *   only) index < num_pub.
  * ADD / SUB / MUL write registers[dst] = a op b; EMIT a yields the value of the
  * next transition constraint, in order (exactly num_constraints EMITs). A register
  * must be written before it is read.
@@ -176,6 +179,41 @@ typedef struct zkp_air_strided_assertion {
 int zkp_air_register_strided(const zkp_air_program* program, const zkp_air_strided_assertion* strided,
                              uint32_t num_strided, int* air_id);
 
+/* Public inputs: one id, many instances. zkp_air_register_params registers a program whose
+ * values may come from the `pub_elems` of each proof instead of from the registration, the
+ * way winterfell's `Air::new(trace_info, pub_inputs, options)` derives them:
+ *  - an operand of kind ZKP_SRC_PUB is pub[index] (degree 0, like a constant),
+ *    index < num_pub and < ZKP_AIR_MAX_PUB_OPERAND;
+ *  - a binding gives an assertion its value from pub (see the kinds below). `index` refers
+ *    to the caller's arrays as passed, before the library sorts them. A bound assertion's
+ *    own value / values must be zero / null; a bound sequence still states num_values.
+ * Refused with ZKP_ERR_ARGUMENT (zkp_air_last_error() names bindings[i] or ops[pc]): num_pub
+ * of 0 or above ZKP_AIR_MAX_PUB, a pub_offset or a sequence run that ends past num_pub, an
+ * index outside its array, an unknown kind, two bindings of one assertion, a bound assertion
+ * that states a value, a PUB operand index >= num_pub. The other rules are those of
+ * zkp_air_register_strided, which is the num_pub = 0 case of this entry (there every
+ * ZKP_SRC_PUB operand is refused).
+ * Under such an id every entry that takes pub_elems (zkp_prove, zkp_prove_device,
+ * zkp_prove_sharded* over one rank, zkp_session_create, zkp_channel_create, zkp_verify)
+ * requires n_pub == num_pub and canonical felts: ZKP_ERR_PUB_INPUTS (zkp_verify:
+ * ZKP_VERIFY_PUB_INPUTS) otherwise. Every value of a proof is that of the concrete program
+ * with pub's values substituted, proved with the same pub_elems: the bytes are identical.
+ * Device: the image cached per (id, n, blowup) holds no value of pub, so instances of one id
+ * do not upload it again. Per proof the pub table goes up once (read by the interpreter
+ * through uniform loads, like the constants), the bound values of the single and periodic
+ * assertions ride the small per-proof value arrays, and each sequence is interpolated on
+ * the device (gather from the pub table, inverse NTT of size k, twist and scale) in three
+ * buffers shared by all instances, instead of once per registration on the host. */
+enum { ZKP_SRC_PUB = 5 };
+enum { ZKP_AIR_MAX_PUB = 1 << 19, ZKP_AIR_MAX_PUB_OPERAND = 1 << 13 };
+enum { ZKP_BIND_ASSERTION = 0,   /* assertions[index].value       = pub[pub_offset] */
+       ZKP_BIND_STRIDED   = 1 }; /* strided[index]: periodic value = pub[pub_offset];
+                                    sequence values[i]             = pub[pub_offset + i] */
+typedef struct zkp_air_binding { uint32_t kind, index; uint64_t pub_offset; } zkp_air_binding;
+int zkp_air_register_params(const zkp_air_program* program, const zkp_air_strided_assertion* strided,
+                            uint32_t num_strided, uint32_t num_pub, const zkp_air_binding* bindings,
+                            uint32_t num_bindings, int* air_id);
+
 /* Checks that need the trace length n. A registered id's entry points return
  * ZKP_ERR_PUB_INPUTS (zkp_verify: ZKP_VERIFY_PUB_INPUTS) for:
  *  - a width other than the program's;
@@ -214,6 +252,13 @@ int zkp_air_register_strided(const zkp_air_program* program, const zkp_air_strid
  * the built-in ids return ZKP_ERR_UNSUPPORTED_AIR. */
 int zkp_air_check_trace(int air_id, const zkp_felt* trace_cols, uint32_t width, uint64_t n, uint64_t* bad_row,
                         uint32_t* bad_constraint, uint32_t* bad_assertion);
+/* The same for an id of zkp_air_register_params, against the instance that pub_elems states
+ * (n_pub == num_pub, canonical felts: ZKP_ERR_PUB_INPUTS otherwise); it also takes an id
+ * without public inputs with n_pub = 0. zkp_air_check_trace itself returns ZKP_ERR_PUB_INPUTS
+ * for an id with public inputs. */
+int zkp_air_check_trace_pub(int air_id, const zkp_felt* pub_elems, uint64_t n_pub, const zkp_felt* trace_cols,
+                            uint32_t width, uint64_t n, uint64_t* bad_row, uint32_t* bad_constraint,
+                            uint32_t* bad_assertion);
 
 /* winterfell `BatchingMethod`. */
 enum { ZKP_BATCHING_LINEAR = 0, ZKP_BATCHING_ALGEBRAIC = 1, ZKP_BATCHING_HORNER = 2 };
@@ -326,6 +371,12 @@ int zkp_prove_device(zkp_ctx* ctx, zkp_air_id air, const void* d_trace_cols, uin
  * winterfell's debug-build validation back calls it before zkp_prove_device. */
 int zkp_air_check_trace_device(zkp_ctx* ctx, int air_id, const void* d_trace_cols, uint32_t width, uint64_t n,
                                uint64_t* bad_row, uint32_t* bad_constraint, uint32_t* bad_assertion);
+/* zkp_air_check_trace_pub for a trace in device memory: the statuses and results of
+ * zkp_air_check_trace_pub, checked as zkp_air_check_trace_device checks. The pub table and
+ * the bound single values go up once per call; the cached image holds no value of pub. */
+int zkp_air_check_trace_device_pub(zkp_ctx* ctx, int air_id, const zkp_felt* pub_elems, uint64_t n_pub,
+                                   const void* d_trace_cols, uint32_t width, uint64_t n, uint64_t* bad_row,
+                                   uint32_t* bad_constraint, uint32_t* bad_assertion);
 
 /* ---- multi-GPU: coset-sharded proving ----
  * One proof is split over `world` ranks by LDE coset (rank r owns the cosets

@@ -94,6 +94,7 @@ EXPORTED = [
     "zkp_channel_draw", "zkp_channel_seed", "zkp_channel_query_positions", "zkp_ctx_trim",
     "zkp_air_register", "zkp_air_unregister", "zkp_air_last_error", "zkp_air_check_trace",
     "zkp_air_check_trace_device", "zkp_air_register_strided",
+    "zkp_air_register_params", "zkp_air_check_trace_pub", "zkp_air_check_trace_device_pub",
 ]
 
 # zkp_host_transport callbacks (include/zkp.h)
@@ -139,6 +140,14 @@ class AirStridedAssertionC(ctypes.Structure):
     """`zkp_air_strided_assertion` (include/zkp.h)."""
     _fields_ = [("column", ctypes.c_uint32), ("num_values", ctypes.c_uint32), ("first_step", ctypes.c_uint64),
                 ("stride", ctypes.c_uint64), ("value", Felt), ("values", ctypes.POINTER(Felt))]
+
+
+class AirBindingC(ctypes.Structure):
+    """`zkp_air_binding` (include/zkp.h)."""
+    _fields_ = [("kind", ctypes.c_uint32), ("index", ctypes.c_uint32), ("pub_offset", ctypes.c_uint64)]
+
+
+BIND_ASSERTION, BIND_STRIDED = 0, 1
 
 
 class AirProgramC(ctypes.Structure):
@@ -285,15 +294,25 @@ def load():
                                           ctypes.POINTER(u32)]
         L.zkp_air_check_trace_device.argtypes = [vp, i32, vp, u32, u64, ctypes.POINTER(u64), ctypes.POINTER(u32),
                                                  ctypes.POINTER(u32)]
+        L.zkp_air_register_params.argtypes = [ctypes.POINTER(AirProgramC), ctypes.POINTER(AirStridedAssertionC), u32,
+                                              u32, ctypes.POINTER(AirBindingC), u32, ctypes.POINTER(i32)]
+        L.zkp_air_check_trace_pub.argtypes = [i32, vp, u64, vp, u32, u64, ctypes.POINTER(u64), ctypes.POINTER(u32),
+                                              ctypes.POINTER(u32)]
+        L.zkp_air_check_trace_device_pub.argtypes = [vp, i32, vp, u64, vp, u32, u64, ctypes.POINTER(u64),
+                                                     ctypes.POINTER(u32), ctypes.POINTER(u32)]
         _lib = L
         return L
 
 
-def air_register(width: int, degrees, constants, periodic, assertions, num_registers: int, ops, strided=()) -> int:
+def air_register(width: int, degrees, constants, periodic, assertions, num_registers: int, ops, strided=(),
+                 num_pub: int = 0, bindings=None, seq_counts=None) -> int:
     """zkp_air_register_strided: `periodic` is a list of value lists, `assertions` (column, step,
     value) triples, `ops` encoded op words, `strided` (column, first_step, stride, value or list of
     values) tuples: an int is `Assertion::periodic`, a list `Assertion::sequence`. Returns the
-    new id; a refused program raises ZkpError with the failing field in its message."""
+    new id; a refused program raises ZkpError with the failing field in its message.
+    With `bindings` not None the entry is zkp_air_register_params: `bindings` holds (kind, index,
+    pub_offset) triples and seq_counts {strided index: num_values} states the length of a bound
+    sequence (whose value in `strided` is 0)."""
     L = load()
     mask = 2**64 - 1
     felts = lambda vals: (Felt * max(1, len(vals)))(*[Felt(int(v) & mask, int(v) >> 64) for v in vals])
@@ -312,8 +331,10 @@ def air_register(width: int, degrees, constants, periodic, assertions, num_regis
     opw = (ctypes.c_uint64 * max(1, len(ops)))(*ops)
     pc.num_registers, pc.num_ops, pc.ops = num_registers, len(ops), opw
     keep, rows = [], []  # the sequences' value arrays stay referenced until the call returns
-    for col, first, stride, val in strided:
-        if isinstance(val, (list, tuple)):
+    for i, (col, first, stride, val) in enumerate(strided):
+        if seq_counts and i in seq_counts:
+            rows.append(AirStridedAssertionC(col, seq_counts[i], first, stride, Felt(0, 0), None))
+        elif isinstance(val, (list, tuple)):
             arr = felts(val)
             keep.append(arr)
             rows.append(AirStridedAssertionC(col, len(val), first, stride, Felt(0, 0), arr))
@@ -321,6 +342,13 @@ def air_register(width: int, degrees, constants, periodic, assertions, num_regis
             rows.append(AirStridedAssertionC(col, 0, first, stride, Felt(int(val) & mask, int(val) >> 64), None))
     sta = (AirStridedAssertionC * max(1, len(rows)))(*rows)
     out = ctypes.c_int()
+    if bindings is not None:
+        bnd = (AirBindingC * max(1, len(bindings)))(*[AirBindingC(k, i, o) for k, i, o in bindings])
+        rc = L.zkp_air_register_params(ctypes.byref(pc), sta, len(rows), num_pub, bnd, len(bindings),
+                                       ctypes.byref(out))
+        if rc:
+            raise ZkpError(rc, "zkp_air_register_params: " + (L.zkp_air_last_error() or b"").decode(errors="replace"))
+        return out.value
     rc = L.zkp_air_register_strided(ctypes.byref(pc), sta, len(rows), ctypes.byref(out))
     if rc:
         entry = "zkp_air_register_strided: " if rows else "zkp_air_register: "
@@ -334,14 +362,20 @@ def air_unregister(air_id: int) -> None:
         raise ZkpError(rc, "zkp_air_unregister")
 
 
-def air_check_trace(air, trace: np.ndarray):
+def air_check_trace(air, trace: np.ndarray, pub=None):
     """zkp_air_check_trace on a (width, n, 2) uint64 column-major trace: None for a valid
-    trace, else (row, constraint, assertion) with None for the part that does not apply."""
+    trace, else (row, constraint, assertion) with None for the part that does not apply.
+    `pub` (the instance's public inputs, for an id registered with them): zkp_air_check_trace_pub."""
     L = load()
     trace = np.ascontiguousarray(trace, dtype=np.uint64)
     row, con, asr = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()
-    rc = L.zkp_air_check_trace(_air(air), trace.ctypes.data, int(trace.shape[0]), int(trace.shape[1]),
-                               ctypes.byref(row), ctypes.byref(con), ctypes.byref(asr))
+    if pub is not None:
+        pubb = b"".join(int(v).to_bytes(16, "little") for v in pub)
+        rc = L.zkp_air_check_trace_pub(_air(air), pubb, len(pub), trace.ctypes.data, int(trace.shape[0]),
+                                       int(trace.shape[1]), ctypes.byref(row), ctypes.byref(con), ctypes.byref(asr))
+    else:
+        rc = L.zkp_air_check_trace(_air(air), trace.ctypes.data, int(trace.shape[0]), int(trace.shape[1]),
+                                   ctypes.byref(row), ctypes.byref(con), ctypes.byref(asr))
     if rc:
         raise ZkpError(rc, "zkp_air_check_trace")
     if row.value == 2**64 - 1:
@@ -494,9 +528,20 @@ class Context:
         """zkp_air_check_trace_device on a (width, n) column-major trace in device memory:
         None for a valid trace, else (row, constraint, assertion) as air_check_trace gives it.
         Registered ids only; synchronises the context's stream."""
+        return self.check_trace_device_pub(air, None, d_trace, width, n)
+
+    def check_trace_device_pub(self, air, pub, d_trace: int, width: int, n: int):
+        """zkp_air_check_trace_device_pub: check_trace_device for an id registered with public
+        inputs, against the instance `pub` states (None: the entry without public inputs)."""
         row, con, asr = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32()
-        rc = self.lib.zkp_air_check_trace_device(self.ptr, _air(air), d_trace, int(width), int(n),
-                                                 ctypes.byref(row), ctypes.byref(con), ctypes.byref(asr))
+        if pub is not None:
+            pubb = b"".join(int(v).to_bytes(16, "little") for v in pub)
+            rc = self.lib.zkp_air_check_trace_device_pub(self.ptr, _air(air), pubb, len(pub), d_trace, int(width),
+                                                         int(n), ctypes.byref(row), ctypes.byref(con),
+                                                         ctypes.byref(asr))
+        else:
+            rc = self.lib.zkp_air_check_trace_device(self.ptr, _air(air), d_trace, int(width), int(n),
+                                                     ctypes.byref(row), ctypes.byref(con), ctypes.byref(asr))
         self._check(rc, "zkp_air_check_trace_device")
         if row.value == 2**64 - 1:
             return None
@@ -505,11 +550,15 @@ class Context:
 
     def check_trace(self, air, trace: np.ndarray):
         """check_trace_device on a host (width, n, 2) uint64 array: alloc, upload, check, free."""
+        return self.check_trace_pub(air, None, trace)
+
+    def check_trace_pub(self, air, pub, trace: np.ndarray):
+        """check_trace_device_pub on a host (width, n, 2) uint64 array."""
         trace = np.ascontiguousarray(trace, dtype=np.uint64)
         d = self.alloc(trace.nbytes)
         try:
             self.to_device(d, trace)
-            return self.check_trace_device(air, d, int(trace.shape[0]), int(trace.shape[1]))
+            return self.check_trace_device_pub(air, pub, d, int(trace.shape[0]), int(trace.shape[1]))
         finally:
             self.free(d)
 
@@ -518,10 +567,11 @@ class Context:
         validate=True (registered ids; a built-in id raises ZkpError UNSUPPORTED_AIR) checks the
         trace on the device first and raises InvalidTrace before any proving work."""
         w, n = int(trace.shape[0]), int(trace.shape[1])
+        vpub = list(pub) if getattr(air_id, "num_pub", 0) else None  # an id with public inputs checks its instance
         air_id = _air(air_id)
         if validate:
-            bad = (self.check_trace(air_id, trace) if device_ptr is None
-                   else self.check_trace_device(air_id, device_ptr, w, n))
+            bad = (self.check_trace_pub(air_id, vpub, trace) if device_ptr is None
+                   else self.check_trace_device_pub(air_id, vpub, device_ptr, w, n))
             if bad is not None:
                 raise InvalidTrace(*bad)
         pubb = b"".join(int(v).to_bytes(16, "little") for v in pub)

@@ -179,8 +179,9 @@ class TrainingUpdateAir:
 # as a straight-line program of field operations that the device runs at every point
 # of the constraint-evaluation domain, periodic columns, and single-row assertions.
 OP_ADD, OP_SUB, OP_MUL, OP_EMIT = 0, 1, 2, 3
-SRC_REG, SRC_CUR, SRC_NEXT, SRC_PERIODIC, SRC_CONST = 0, 1, 2, 3, 4
+SRC_REG, SRC_CUR, SRC_NEXT, SRC_PERIODIC, SRC_CONST, SRC_PUB = 0, 1, 2, 3, 4, 5
 MAX_REGISTERS, MAX_OPS = 32, 8192
+MAX_PUB, MAX_PUB_OPERAND = 1 << 19, 1 << 13
 
 
 class Expr:
@@ -260,19 +261,24 @@ class RegisteredAir:
         self.num_constraints = len(program.constraints)
         self.num_assertions = len(program.assertions) + len(program.strided_assertions)
         self.num_coeffs = self.num_constraints + self.num_assertions  # composition coefficients
+        self.num_pub = program.num_pub  # 0: concrete values; else every proof's pub has this length
 
     def __int__(self):
         return self.AIR_ID
 
     __index__ = __int__
 
-    def check_trace(self, trace):
+    def check_trace(self, trace, pub=None):
         from . import _native
-        return _native.air_check_trace(self.AIR_ID, trace)
+        return _native.air_check_trace(self.AIR_ID, trace, pub)
 
     def check_trace_device(self, ctx, d_trace, n):
         """Context.check_trace_device for this id: the trace (WIDTH x n) is in device memory."""
         return ctx.check_trace_device(self.AIR_ID, d_trace, self.WIDTH, n)
+
+    def check_trace_device_pub(self, ctx, pub, d_trace, n):
+        """The same for an id with public inputs, against the instance `pub` states."""
+        return ctx.check_trace_device_pub(self.AIR_ID, pub, d_trace, self.WIDTH, n)
 
     def close(self):
         if self.AIR_ID is not None:
@@ -303,7 +309,12 @@ class AirProgram:
         air = p.register()          # air.AIR_ID
 
     Values are concrete for one instance (what `Air::new` derives from the public
-    inputs). Equal subexpressions are shared; registers are allocated by a linear scan
+    inputs), or come from each proof's public inputs: `p.pub(i)` is an expression leaf,
+    `assertion(col, step, pub=i)`, `periodic_assertion(..., pub=i)` and
+    `sequence_assertion(..., pub_offset=o, count=k)` bind assertion values, and the program
+    registers once (zkp_air_register_params) for every instance; `num_pub` is the length of
+    pub (by default one past the highest index used). bind(pub) gives the concrete program
+    of one instance. Equal subexpressions are shared; registers are allocated by a linear scan
     over last uses. evaluate() is a pure-Python evaluation of the same constraints."""
 
     def __init__(self, width: int):
@@ -317,6 +328,10 @@ class AirProgram:
         self.constraints = []  # (Expr, degree)
         self.assertions = []   # (column, step, value)
         self.strided_assertions = []  # (column, first_step, stride, value | [values])
+        self.bound = {}          # index into assertions -> pub index
+        self.strided_bound = {}  # index into strided_assertions -> (pub offset, count or None)
+        self._num_pub = None     # set_num_pub(); None: one past the highest pub index used
+        self._pub_top = 0
 
     # -- expression nodes
     def _leaf(self, kind, index):
@@ -342,6 +357,29 @@ class AirProgram:
             self.constants.append(v)
         return self._leaf("const", self._const_index[v])
 
+    def _use_pub(self, i, run=1):
+        i = int(i)
+        if i < 0 or run < 1 or i + run > MAX_PUB:
+            raise IndexError(f"public input {i} (run {run}) outside 0..{MAX_PUB}")
+        self._pub_top = max(self._pub_top, i + run)
+        return i
+
+    def pub(self, i) -> Expr:
+        """Public input i of the proof's `pub` (degree 0, like a constant)."""
+        i = self._use_pub(i)
+        if i >= MAX_PUB_OPERAND:
+            raise IndexError(f"a public input used as an operand must have an index below {MAX_PUB_OPERAND}")
+        return self._leaf("pub", i)
+
+    def set_num_pub(self, n: int):
+        """The length every proof's `pub` must have (pub may be longer than what the program
+        reads: the whole of it seeds the coin)."""
+        self._num_pub = int(n)
+
+    @property
+    def num_pub(self) -> int:
+        return self._pub_top if self._num_pub is None else self._num_pub
+
     def periodic(self, values) -> Expr:
         """A periodic column: `values` repeats along the trace (a power-of-two cycle in 2..1024)."""
         self.periodic_columns.append([int(v) % P for v in values])
@@ -354,19 +392,76 @@ class AirProgram:
             expr = self.const(expr)
         self.constraints.append((expr, int(degree)))
 
-    def assertion(self, column: int, step: int, value: int):
-        """`Assertion::single(column, step, value)`."""
-        self.assertions.append((int(column), int(step), int(value) % P))
+    def assertion(self, column: int, step: int, value: int = None, pub: int = None):
+        """`Assertion::single(column, step, value)`; with pub=i the value is pub[i] of each proof."""
+        if (value is None) == (pub is None):
+            raise ValueError("an assertion takes a value or pub=, not both")
+        if pub is not None:
+            self.bound[len(self.assertions)] = self._use_pub(pub)
+        self.assertions.append((int(column), int(step), 0 if pub is not None else int(value) % P))
 
-    def periodic_assertion(self, column: int, first_step: int, stride: int, value: int):
-        """`Assertion::periodic(column, first_step, stride, value)`: the column holds `value` at
-        first_step + stride * i for every i < n / stride (stride a power of two >= 2)."""
-        self.strided_assertions.append((int(column), int(first_step), int(stride), int(value) % P))
+    def periodic_assertion(self, column: int, first_step: int, stride: int, value: int = None, pub: int = None):
+        """`Assertion::periodic(column, first_step, stride, value)`: the column holds `value` (or
+        pub[pub]) at first_step + stride * i for every i < n / stride (stride a power of two >= 2)."""
+        if (value is None) == (pub is None):
+            raise ValueError("an assertion takes a value or pub=, not both")
+        if pub is not None:
+            self.strided_bound[len(self.strided_assertions)] = (self._use_pub(pub), None)
+        self.strided_assertions.append((int(column), int(first_step), int(stride),
+                                        0 if pub is not None else int(value) % P))
 
-    def sequence_assertion(self, column: int, first_step: int, stride: int, values):
+    def sequence_assertion(self, column: int, first_step: int, stride: int, values=None, pub_offset: int = None,
+                           count: int = None):
         """`Assertion::sequence(column, first_step, stride, values)`: the column holds values[i] at
-        first_step + stride * i; len(values) = n / stride, a power of two."""
+        first_step + stride * i; len(values) = n / stride, a power of two. With pub_offset=o,
+        count=k the values are pub[o .. o + k)."""
+        if (values is None) == (pub_offset is None):
+            raise ValueError("a sequence takes values or pub_offset= and count=, not both")
+        if pub_offset is not None:
+            if count is None or int(count) < 1:
+                raise ValueError("a bound sequence states count=")
+            self.strided_bound[len(self.strided_assertions)] = (self._use_pub(pub_offset, int(count)), int(count))
+            self.strided_assertions.append((int(column), int(first_step), int(stride), 0))
+            return
         self.strided_assertions.append((int(column), int(first_step), int(stride), [int(v) % P for v in values]))
+
+    def bind(self, pub) -> "AirProgram":
+        """The concrete program of the instance `pub`: every pub leaf a constant, every bound
+        assertion its value. It registers through the entries without public inputs; a proof
+        under it equals, byte for byte, the proof under this program's id with the same pub."""
+        pub = [int(v) % P for v in pub]
+        if len(pub) != self.num_pub:
+            raise ValueError(f"pub has {len(pub)} elements, the program takes {self.num_pub}")
+        out = AirProgram(self.width)
+        made = {}
+        for nd in self._nodes:
+            if nd.kind in ("cur", "next"):
+                made[nd.id] = out._leaf(nd.kind, nd.a)
+            elif nd.kind == "periodic":
+                while len(out.periodic_columns) <= nd.a:
+                    out.periodic(self.periodic_columns[len(out.periodic_columns)])
+                made[nd.id] = out._leaf("periodic", nd.a)
+            elif nd.kind == "const":
+                made[nd.id] = out.const(self.constants[nd.a])
+            elif nd.kind == "pub":
+                made[nd.id] = out.const(pub[nd.a])
+            else:
+                made[nd.id] = out._op(nd.kind, made[nd.a.id], made[nd.b.id])
+        while len(out.periodic_columns) < len(self.periodic_columns):
+            out.periodic(self.periodic_columns[len(out.periodic_columns)])
+        for e, d in self.constraints:
+            out.constraint(made[e.id], d)
+        for i, (c, s, v) in enumerate(self.assertions):
+            out.assertion(c, s, pub[self.bound[i]] if i in self.bound else v)
+        for i, (c, f, st, v) in enumerate(self.strided_assertions):
+            if i in self.strided_bound:
+                o, k = self.strided_bound[i]
+                v = pub[o] if k is None else pub[o:o + k]
+            if isinstance(v, list):
+                out.sequence_assertion(c, f, st, v)
+            else:
+                out.periodic_assertion(c, f, st, v)
+        return out
 
     def sorted_assertions(self):
         """The single assertions in the order their composition coefficients are drawn: (step, column)."""
@@ -378,14 +473,15 @@ class AirProgram:
         return sorted(self.strided_assertions, key=lambda a: (a[2], a[1], a[0]))
 
     # -- the spec
-    def evaluate(self, cur_row, next_row, row_index: int = 0, periodic=None):
+    def evaluate(self, cur_row, next_row, row_index: int = 0, periodic=None, pub=None):
         """Every constraint's value on the frame (cur_row, next_row) at trace row `row_index`
         (periodic columns take values[row_index % cycle]); big-int arithmetic mod P. Off the
-        trace domain, `periodic` gives the periodic columns' values at the frame's point."""
+        trace domain, `periodic` gives the periodic columns' values at the frame's point.
+        `pub`: the instance's public inputs, for a program that reads them."""
         per = list(periodic) if periodic is not None else [c[row_index % len(c)] for c in self.periodic_columns]
-        return self._evaluate(cur_row, next_row, per)
+        return self._evaluate(cur_row, next_row, per, pub)
 
-    def _evaluate(self, cur_row, next_row, per):
+    def _evaluate(self, cur_row, next_row, per, pub=None):
         val = [0] * len(self._nodes)
         for nd in self._nodes:
             if nd.kind == "cur":
@@ -396,6 +492,8 @@ class AirProgram:
                 v = per[nd.a]
             elif nd.kind == "const":
                 v = self.constants[nd.a]
+            elif nd.kind == "pub":
+                v = int(pub[nd.a])
             elif nd.kind == "add":
                 v = val[nd.a.id] + val[nd.b.id]
             elif nd.kind == "sub":
@@ -409,7 +507,7 @@ class AirProgram:
     def compile(self) -> CompiledProgram:
         """Ops in dependency order, each constraint's EMIT right after its value; registers
         from a linear scan over last uses (a register is free again after its last read)."""
-        leaf = {"cur": SRC_CUR, "next": SRC_NEXT, "periodic": SRC_PERIODIC, "const": SRC_CONST}
+        leaf = {"cur": SRC_CUR, "next": SRC_NEXT, "periodic": SRC_PERIODIC, "const": SRC_CONST, "pub": SRC_PUB}
         code = {"add": OP_ADD, "sub": OP_SUB, "mul": OP_MUL}
         order, placed = [], set()   # ("op", node) / ("emit", node)
         for root, _ in self.constraints:
@@ -460,16 +558,28 @@ class AirProgram:
         return CompiledProgram(ops, max(used, 1))
 
     def register(self) -> RegisteredAir:
-        """zkp_air_register_strided: validates the program and returns its id holder."""
+        """zkp_air_register_strided, or zkp_air_register_params for a program that reads public
+        inputs: validates the program and returns its id holder."""
         from . import _native
         cp = self.compile()
+        bindings = seq_counts = None
+        if self.num_pub:
+            bindings = [(_native.BIND_ASSERTION, i, o) for i, o in sorted(self.bound.items())]
+            bindings += [(_native.BIND_STRIDED, i, o) for i, (o, _) in sorted(self.strided_bound.items())]
+            seq_counts = {i: k for i, (_, k) in self.strided_bound.items() if k is not None}
         aid = _native.air_register(self.width, [d for _, d in self.constraints], self.constants,
                                    self.periodic_columns, self.assertions, cp.num_registers, cp.ops,
-                                   self.strided_assertions)
+                                   self.strided_assertions, self.num_pub, bindings, seq_counts)
         return RegisteredAir(aid, self)
 
-    def check_trace(self, trace):
+    def check_trace(self, trace, pub=None):
         """zkp_air_check_trace on a (width, n, 2) uint64 column-major trace: None when every
-        transition and assertion holds, else (row, constraint, assertion)."""
+        transition and assertion holds, else (row, constraint, assertion). `pub`: the instance,
+        for a program that reads public inputs."""
         with self.register() as air:
-            return air.check_trace(trace)
+            return air.check_trace(trace, pub)
+
+    def check_trace_device(self, ctx, trace, pub=None):
+        """The same check on the device (Context.check_trace on a host trace)."""
+        with self.register() as air:
+            return ctx.check_trace_pub(air, pub, trace)

@@ -453,55 +453,32 @@ int zkp_kernel_stats_table(zkp_ctx* ctx, char** table) {
   });
 }
 
-// ---- caller-defined AIRs: the table of constraint programs (air_program.hpp). Host-only.
-int zkp_air_register(const zkp_air_program* program, int* air_id) {
-  return zkp_air_register_strided(program, nullptr, 0, air_id);
-}
-
-int zkp_air_register_strided(const zkp_air_program* program, const zkp_air_strided_assertion* strided,
-                             uint32_t num_strided, int* air_id) {
-  std::string& err = airp::last_error();
-  err.clear();
-  try {
-    if (!air_id) {
-      err = "air_id: null";
-      return ZKP_ERR_ARGUMENT;
-    }
-    auto p = std::make_shared<airp::Program>();
-    err = airp::validate(program, *p);
-    if (err.empty()) err = airp::validate_strided(strided, num_strided, *p);
-    if (!err.empty()) return ZKP_ERR_ARGUMENT;
-    *air_id = airp::insert(std::move(p));
-    return ZKP_OK;
-  } catch (const std::bad_alloc&) {
-    return ZKP_ERR_OOM;
-  } catch (...) {
-    return ZKP_ERR_ARGUMENT;
-  }
-}
-
-int zkp_air_unregister(int air_id) {
-  std::string& err = airp::last_error();
-  err.clear();
-  if (airp::erase(air_id)) return ZKP_OK;
-  err = "air_id: not a registered id";
-  return ZKP_ERR_ARGUMENT;
-}
-
-const char* zkp_air_last_error(void) { return airp::last_error().c_str(); }
-
 // zkp_air_check_trace on a trace in device memory (k_check_program). Every status is
 // decided on the host, in zkp_air_check_trace's order, before the first HIP call.
 int zkp_air_check_trace_device(zkp_ctx* ctx, int air_id, const void* d_trace_cols, uint32_t width, uint64_t n,
                                uint64_t* bad_row, uint32_t* bad_constraint, uint32_t* bad_assertion) {
-  if (!ctx || !d_trace_cols || !bad_row || !bad_constraint || !bad_assertion) return ZKP_ERR_ARGUMENT;
+  return zkp_air_check_trace_device_pub(ctx, air_id, nullptr, 0, d_trace_cols, width, n, bad_row, bad_constraint,
+                                        bad_assertion);
+}
+
+// With public inputs (zkp_air_register_params) the cached image holds no value of pub: the
+// pub table and the singles' values go up per call, and a bound strided assertion's cells
+// read the pub table (ProgStridedCells::pub1).
+int zkp_air_check_trace_device_pub(zkp_ctx* ctx, int air_id, const zkp_felt* pub_elems, uint64_t n_pub,
+                                   const void* d_trace_cols, uint32_t width, uint64_t n, uint64_t* bad_row,
+                                   uint32_t* bad_constraint, uint32_t* bad_assertion) {
+  if (!ctx || !d_trace_cols || !bad_row || !bad_constraint || !bad_assertion || (n_pub && !pub_elems))
+    return ZKP_ERR_ARGUMENT;
   return guarded(ctx, [&] {
     if (air_id == ZKP_AIR_MIMC || air_id == ZKP_AIR_GLOBAL_UPDATE || air_id == ZKP_AIR_TRAINING_UPDATE)
       return (int)ZKP_ERR_UNSUPPORTED_AIR;
     if (n < 8 || (n & (n - 1)) || width == 0 || width > 255) return (int)ZKP_ERR_TRACE_SHAPE;
     AirDesc air;
-    const int rc = build_air(air, air_id, width, n, {});
+    std::vector<felt> pub(n_pub);
+    for (uint64_t i = 0; i < n_pub; i++) pub[i] = make(pub_elems[i].lo, pub_elems[i].hi);
+    const int rc = build_air(air, air_id, width, n, pub);
     if (rc) return rc;
+    if (!air.prog->num_pub && n_pub) return (int)ZKP_ERR_PUB_INPUTS;
     if (n > (1ull << MAX_LOG_TRACE)) return (int)ZKP_ERR_TRACE_SHAPE;  // the result key holds 23 bits of row
     const airp::Program& pr = *air.prog;
     HIP_CHECK(hipSetDevice(ctx->device));
@@ -516,7 +493,7 @@ int zkp_air_check_trace_device(zkp_ctx* ctx, int air_id, const void* d_trace_col
     const std::vector<airp::Strided>& sv = pr.strided;
     const size_t S = sv.size();
     size_t seq_felts = 0;
-    for (const airp::Strided& a : sv) seq_felts += a.values.size();
+    for (const airp::Strided& a : sv) seq_felts += a.pub < 0 ? a.values.size() : 0;  // bound ones are read from pub
     const size_t o_step = o_col + (A + 3) / 4, o_val = o_step + (A + 3) / 4, o_sdesc = o_val + A,
                  o_svals = o_sdesc + 3 * S, total = o_svals + seq_felts;
     uint64_t strided_blocks = 0;
@@ -534,16 +511,20 @@ int zkp_air_check_trace_device(zkp_ctx* ctx, int air_id, const void* d_trace_col
       for (size_t k = 0; k < A; k++) steps[k] = (uint32_t)pr.a_step[k];  // < n <= 2^23 (build_air)
       if (A) {
         memcpy(img.data() + o_col, pr.a_col.data(), A * 4);
-        memcpy(img.data() + o_val, pr.a_val.data(), A * 16);
+        if (!pr.num_pub) memcpy(img.data() + o_val, pr.a_val.data(), A * 16);
       }
       ProgStridedCells* cells = reinterpret_cast<ProgStridedCells*>(img.data() + o_sdesc);
       uint32_t blk = 0, voff = 0;
       for (size_t j = 0; j < S; j++) {
         const uint32_t count = (uint32_t)(n / sv[j].stride);
+        const bool bound = sv[j].pub >= 0;
         cells[j] = ProgStridedCells{sv[j].col, (uint32_t)sv[j].first, (uint32_t)sv[j].stride, count, blk,
-                                    sv[j].sequence() ? voff : 0xffffffffu, {0, 0}, sv[j].val};
-        if (sv[j].sequence()) memcpy(img.data() + o_svals + voff, sv[j].values.data(), (size_t)count * 16);
-        voff += (uint32_t)sv[j].values.size();
+                                    sv[j].sequence() ? voff : 0xffffffffu, bound ? (uint32_t)sv[j].pub + 1 : 0, 0,
+                                    bound ? zero() : sv[j].val};
+        if (sv[j].sequence() && !bound) {
+          memcpy(img.data() + o_svals + voff, sv[j].values.data(), (size_t)count * 16);
+          voff += count;
+        }
         blk += (count + 63) / 64;
       }
       // singles alone: at most 224 KiB, staged in the pinned ring. Sequence values can take it
@@ -558,6 +539,16 @@ int zkp_air_check_trace_device(zkp_ctx* ctx, int air_id, const void* d_trace_col
     ca.a_col = reinterpret_cast<const uint32_t*>(dimg + o_col);
     ca.a_step = reinterpret_cast<const uint32_t*>(dimg + o_step);
     ca.a_val = dimg + o_val;
+    if (pr.num_pub) {
+      // the instance's values: the pub table (larger than the ring's 1 MiB it is copied from
+      // `pr.pub`, which lives until the download below has synchronised) and the singles' values
+      felt* dpub = ctx->buf<felt>("check_pub", pr.num_pub);
+      ctx->upload(dpub, pr.pub.data(), (size_t)pr.num_pub * 16);
+      ca.code.pub = dpub;
+      felt* dval = ctx->buf<felt>("check_aval", A);
+      if (A) ctx->upload(dval, pr.a_val.data(), A * 16);
+      ca.a_val = dval;
+    }
     ca.n = n;
     ca.nstrided = (uint32_t)S;
     ca.sdesc = reinterpret_cast<const ProgStridedCells*>(dimg + o_sdesc);

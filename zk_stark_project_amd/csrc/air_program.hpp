@@ -25,7 +25,9 @@ struct Strided {
   uint64_t first = 0, stride = 0;
   felt val = {};
   std::vector<felt> values;
-  bool sequence() const { return !values.empty(); }
+  uint32_t nvals = 0;  // a sequence's num_values; `values` is empty while it is bound and not yet instantiated
+  int64_t pub = -1;    // zkp_air_register_params: the value(s) are pub[pub ...]; -1 = concrete
+  bool sequence() const { return nvals != 0; }
   felt value_at(uint64_t i) const { return values.empty() ? val : values[i]; }
 };
 
@@ -42,6 +44,12 @@ struct Program {
   std::vector<uint64_t> a_step;
   std::vector<felt> a_val;
   std::vector<uint64_t> ops;
+  // zkp_air_register_params: a_pub[k] = the pub offset of stored single assertion k, or -1.
+  // `pub` is empty in the registered program and holds the instance's public inputs in the
+  // copy that instantiate() makes, where every bound value is filled in.
+  uint32_t num_pub = 0;
+  std::vector<int64_t> a_pub;
+  std::vector<felt> pub;
   uint32_t max_cycle() const {
     uint32_t m = 0;
     for (auto& c : periodic) m = std::max<uint32_t>(m, (uint32_t)c.size());
@@ -51,7 +59,8 @@ struct Program {
 
 // Checks every rule of zkp_air_program that does not depend on the trace length and
 // fills `out`; returns the empty string, or a message naming the failing field.
-inline std::string validate(const zkp_air_program* p, Program& out) {
+inline std::string validate(const zkp_air_program* p, Program& out, uint32_t num_pub = 0,
+                            std::vector<uint32_t>* single_order = nullptr) {
   auto idx = [](const char* what, size_t i, const std::string& why) {
     return std::string(what) + "[" + std::to_string(i) + "]: " + why;
   };
@@ -115,7 +124,10 @@ inline std::string validate(const zkp_air_program* p, Program& out) {
       out.a_step.push_back(a.step);
       out.a_val.push_back(make(a.value.lo, a.value.hi));
     }
+    out.a_pub.assign(p->num_assertions, -1);
+    if (single_order) *single_order = order;  // stored position k holds the caller's assertions[order[k]]
   }
+  out.num_pub = num_pub;
   if (p->num_registers < 1 || p->num_registers > ZKP_AIR_MAX_REGISTERS) return "num_registers: must be 1..32";
   if (p->num_ops < 1 || p->num_ops > ZKP_AIR_MAX_OPS) return "num_ops: must be 1..8192";
   if (!p->ops) return "ops: null";
@@ -149,6 +161,10 @@ inline std::string validate(const zkp_air_program* p, Program& out) {
           break;
         case ZKP_SRC_CONST:
           if (i >= p->num_constants) err = "constant outside num_constants";
+          break;
+        case ZKP_SRC_PUB:
+          if (!num_pub) err = "unknown operand kind";  // the entries without public inputs
+          else if (i >= num_pub) err = "public input outside num_pub";
           break;
         default:
           err = "unknown operand kind";
@@ -184,7 +200,8 @@ inline std::string validate(const zkp_air_program* p, Program& out) {
 // The strided assertions of zkp_air_register_strided against a program that validate()
 // has filled: every rule that does not depend on the trace length. Returns the empty
 // string, or a message naming strided[i].
-inline std::string validate_strided(const zkp_air_strided_assertion* s, uint32_t count, Program& out) {
+inline std::string validate_strided(const zkp_air_strided_assertion* s, uint32_t count, Program& out,
+                                    const std::vector<int64_t>* bound = nullptr) {
   auto idx = [](size_t i, const std::string& why) { return "strided[" + std::to_string(i) + "]: " + why; };
   if (!count) return "";
   if (!s) return "strided: null";
@@ -203,10 +220,11 @@ inline std::string validate_strided(const zkp_air_strided_assertion* s, uint32_t
       if (ge_p(make(a.value.lo, a.value.hi))) return idx(i, "value not a canonical field element");
       continue;
     }
-    if (!a.values) return idx(i, "values: null");
+    const bool is_bound = bound && (*bound)[i] >= 0;  // its values come from pub (validate_bindings)
+    if (!a.values && !is_bound) return idx(i, "values: null");
     seq_values += a.num_values;
     if (seq_values > ZKP_AIR_MAX_SEQUENCE_VALUES) return idx(i, "more than 2^18 sequence values in the program");
-    for (uint32_t j = 0; j < a.num_values; j++)
+    for (uint32_t j = 0; j < a.num_values && !is_bound; j++)
       if (ge_p(make(a.values[j].lo, a.values[j].hi)))
         return idx(i, "values[" + std::to_string(j) + "] not a canonical field element");
   }
@@ -236,10 +254,62 @@ inline std::string validate_strided(const zkp_air_strided_assertion* s, uint32_t
     d.first = a.first_step;
     d.stride = a.stride;
     d.val = a.num_values ? zero() : make(a.value.lo, a.value.hi);
-    for (uint32_t j = 0; j < a.num_values; j++) d.values.push_back(make(a.values[j].lo, a.values[j].hi));
+    d.nvals = a.num_values;
+    d.pub = bound ? (*bound)[order[k]] : -1;
+    for (uint32_t j = 0; j < a.num_values && d.pub < 0; j++) d.values.push_back(make(a.values[j].lo, a.values[j].hi));
     out.strided.push_back(std::move(d));
   }
   return "";
+}
+
+// The bindings of zkp_air_register_params, before the assertions are sorted: every rule of
+// include/zkp.h. single[i] / strided[i] receive the pub offset of the caller's assertions[i] /
+// strided[i], or -1. Returns the empty string, or a message naming bindings[i].
+inline std::string validate_bindings(const zkp_air_program* p, const zkp_air_strided_assertion* s, uint32_t num_strided,
+                                     uint32_t num_pub, const zkp_air_binding* b, uint32_t count,
+                                     std::vector<int64_t>& single, std::vector<int64_t>& strided) {
+  auto idx = [](size_t i, const std::string& why) { return "bindings[" + std::to_string(i) + "]: " + why; };
+  single.assign(p->num_assertions, -1);
+  strided.assign(num_strided, -1);
+  if (count && !b) return "bindings: null";
+  if (num_strided && !s) return "strided: null";
+  for (uint32_t i = 0; i < count; i++) {
+    uint64_t run = 1;
+    if (b[i].kind == ZKP_BIND_ASSERTION) {
+      if (b[i].index >= p->num_assertions) return idx(i, "index outside the assertions");
+      if (single[b[i].index] >= 0) return idx(i, "the assertion is bound twice");
+      const zkp_felt v = p->assertions[b[i].index].value;
+      if (v.lo | v.hi) return idx(i, "a bound assertion's own value must be zero");
+    } else if (b[i].kind == ZKP_BIND_STRIDED) {
+      if (b[i].index >= num_strided) return idx(i, "index outside the strided assertions");
+      if (strided[b[i].index] >= 0) return idx(i, "the assertion is bound twice");
+      const zkp_air_strided_assertion& a = s[b[i].index];
+      if (a.value.lo | a.value.hi) return idx(i, "a bound assertion's own value must be zero");
+      if (a.values) return idx(i, "a bound sequence's own values must be null");
+      if (a.num_values) run = a.num_values;
+    } else {
+      return idx(i, "unknown kind");
+    }
+    if (b[i].pub_offset >= num_pub || run > num_pub - b[i].pub_offset)
+      return idx(i, "pub_offset (or the sequence's run from it) ends past num_pub");
+    (b[i].kind == ZKP_BIND_ASSERTION ? single : strided)[b[i].index] = (int64_t)b[i].pub_offset;
+  }
+  return "";
+}
+
+// The instance of a program with public inputs that `pub` states (num_pub canonical felts,
+// checked by the caller): a copy that carries pub and every bound value.
+inline std::shared_ptr<const Program> instantiate(const Program& pr, const std::vector<felt>& pub) {
+  auto b = std::make_shared<Program>(pr);
+  b->pub = pub;
+  for (size_t k = 0; k < b->a_pub.size(); k++)
+    if (b->a_pub[k] >= 0) b->a_val[k] = pub[b->a_pub[k]];
+  for (Strided& s : b->strided) {
+    if (s.pub < 0) continue;
+    if (s.sequence()) s.values.assign(pub.begin() + s.pub, pub.begin() + s.pub + s.nvals);
+    else s.val = pub[s.pub];
+  }
+  return b;
 }
 
 // The program on one frame: out[i] = constraint i (per[p] = periodic column p at the
@@ -253,6 +323,7 @@ inline void evaluate(const Program& pr, const felt* cur, const felt* nxt, const 
       case ZKP_SRC_CUR: return cur[i];
       case ZKP_SRC_NEXT: return nxt[i];
       case ZKP_SRC_PERIODIC: return per[i];
+      case ZKP_SRC_PUB: return pr.pub[i];
       default: return pr.consts[i];
     }
   };

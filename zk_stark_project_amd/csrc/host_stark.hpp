@@ -254,16 +254,24 @@ inline int build_air(AirDesc& a, int id, uint32_t w, uint64_t n, const std::vect
     return 0;
   }
   if (auto pr = airp::lookup(id)) {
-    // a registered constraint program (air_program.hpp): its values are concrete, pub only seeds the coin
+    // a registered constraint program (air_program.hpp). Without public inputs its values are
+    // concrete and pub only seeds the coin; with them (zkp_air_register_params) pub must be the
+    // num_pub canonical felts of an instance, and the program used from here on is that instance
     if (w != pr->width || pr->max_cycle() > n) return ZKP_ERR_PUB_INPUTS;
+    if (pr->num_pub) {
+      if (pub.size() != pr->num_pub) return ZKP_ERR_PUB_INPUTS;
+      for (const felt& v : pub)
+        if (ge_p(v)) return ZKP_ERR_PUB_INPUTS;
+    }
     for (uint64_t s : pr->a_step)
       if (s >= n) return ZKP_ERR_PUB_INPUTS;
     for (const airp::Strided& s : pr->strided)
-      if (s.stride > n || (s.sequence() && s.values.size() * s.stride != n)) return ZKP_ERR_PUB_INPUTS;
+      if (s.stride > n || (s.sequence() && s.nvals * s.stride != n)) return ZKP_ERR_PUB_INPUTS;
     // A constraint of degree d over n rows has a quotient of degree (d-1)(n-1), and comp_cols()
     // (winterfell's count) provides ceil((d-1)(n-1)/n) columns of n coefficients: one short
     // exactly when n divides d-1. No proof of such a shape verifies.
     if (pr->base_degree > 1 && (pr->base_degree - 1) % n == 0) return ZKP_ERR_PUB_INPUTS;
+    if (pr->num_pub) pr = airp::instantiate(*pr, pub);
     a.num_t = pr->num_t;
     a.base_degree = pr->base_degree;
     a.cycle = 0;

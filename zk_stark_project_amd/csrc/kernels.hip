@@ -472,6 +472,7 @@ __device__ __forceinline__ void run_program(const ProgCode& p, lds_u32x4* rg, co
         const ProgPeriodic d = p.per_desc[idx];
         return p.per_tab[d.off + (per_index & d.mask)];
       }
+      case ZKP_SRC_PUB: return p.pub[idx];
       default: return p.consts[idx];
     }
   };
@@ -569,6 +570,29 @@ __global__ __launch_bounds__(TPB) void k_strided_combine(ProgSeqArgs a, uint32_t
   out[(uint64_t)g * n + p] = s;
 }
 
+// The sequences of a program with public inputs (ProgPubSeqArgs): sequence d = blockIdx.y, one
+// value per thread; the descriptor is a uniform load. Gather: the k values from the pub table
+// (or a concrete sequence's from the image) into the layout the inverse NTT reads.
+__global__ __launch_bounds__(TPB) void k_prog_seq_gather(ProgPubSeqArgs a, felt* __restrict__ vals) {
+  const ProgPubSeq d = a.desc[blockIdx.y];
+  const uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= (1ull << d.logk)) return;
+  vals[d.off + i] = d.pub1 ? a.pub[d.pub1 - 1 + i] : a.raw[d.off + i];
+}
+// Twist: coefficient i of V_d from the NTT's bit-reversed, k-scaled output, times n / k and
+// w_n^(-first i) (first * i < n: first < stride, i < k; the table holds the exponents below n/2,
+// the others are the negated entry n/2 lower), in the natural order k_strided_combine reads.
+__global__ __launch_bounds__(TPB) void k_prog_seq_twist(ProgPubSeqArgs a, const felt* __restrict__ ntt,
+                                                        felt* __restrict__ tab) {
+  const ProgPubSeq d = a.desc[blockIdx.y];
+  const uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= (1ull << d.logk)) return;
+  const uint64_t half = 1ull << (a.logn - 1), e = (uint64_t)d.first * i;
+  const felt tw = e < half ? a.itwn[e] : sub(zero(), a.itwn[e - half]);
+  const felt c = ntt[d.off + (d.logk ? rev_bits((uint32_t)i, d.logk) : 0)];
+  tab[d.off + i] = mul(mul(c, make(1ull << (a.logn - d.logk), 0)), tw);
+}
+
 // A natural (column-major, not extended) trace against a registered constraint
 // program: what zkp_air_check_trace does on the host. Blocks [0, frame_blocks) take one
 // frame (rows r, r + 1) per thread, r in [0, n - 2]: row n - 1 starts no frame and nothing
@@ -610,7 +634,11 @@ __global__ __launch_bounds__(PROG_TPB) void k_check_program(ProgCheckArgs a, con
       const uint32_t i = (sb - d.blk0) * PROG_TPB + threadIdx.x;
       if (i < d.count) {
         const uint64_t row = d.first + (uint64_t)d.stride * i;
-        const felt want = d.voff != 0xffffffffu ? a.svals[d.voff + i] : d.val;
+        // a bound assertion's value is the instance's: pub[pub1 - 1], a sequence's cell i the i-th from there
+        const bool seq = d.voff != 0xffffffffu;
+        const felt* const src = d.pub1 ? a.code.pub + (d.pub1 - 1) : a.svals + d.voff;
+        felt want = d.val;
+        if (d.pub1 || seq) want = src[seq ? i : 0];
         fail = !eq(T[(uint64_t)d.col * a.n + row], want);
         key = ((unsigned long long)(a.nassert + lo) << 32) | row;
       }
@@ -1605,6 +1633,17 @@ void launch_strided_combine(Prof& prof, hipStream_t s, const ProgSeqArgs& a, uin
   LAUNCH(prof, "strided_combine", s, (double)a.ngroups * (double)(1ull << logn) * 16.0,
          hipLaunchKernelGGL(k_strided_combine, dim3(blocks_for(1ull << logn), a.ngroups), dim3(TPB), 0, s, a, logn,
                             out));
+}
+
+void launch_prog_seq_gather(Prof& prof, hipStream_t s, const ProgPubSeqArgs& a, uint64_t maxk, felt* vals) {
+  LAUNCH(prof, "prog_seq_gather", s, (double)a.nseq * maxk * 32.0,
+         hipLaunchKernelGGL(k_prog_seq_gather, dim3(blocks_for(maxk), a.nseq), dim3(TPB), 0, s, a, vals));
+}
+
+void launch_prog_seq_twist(Prof& prof, hipStream_t s, const ProgPubSeqArgs& a, uint64_t maxk, const felt* ntt,
+                           felt* tab) {
+  LAUNCH(prof, "prog_seq_twist", s, (double)a.nseq * maxk * 48.0,
+         hipLaunchKernelGGL(k_prog_seq_twist, dim3(blocks_for(maxk), a.nseq), dim3(TPB), 0, s, a, ntt, tab));
 }
 
 void launch_check_program(Prof& prof, hipStream_t s, ProgCheckArgs a, uint32_t width, const felt* T,

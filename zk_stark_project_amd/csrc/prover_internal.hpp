@@ -410,7 +410,7 @@ struct ProgCodeLayout {
   }
   ProgCode code(const felt* dimg) const {
     return ProgCode{reinterpret_cast<const uint64_t*>(dimg), (uint32_t)pr.ops.size(), pr.nreg, dimg + o_const,
-                    reinterpret_cast<const ProgPeriodic*>(dimg + o_desc), dimg + tab[0]};
+                    reinterpret_cast<const ProgPeriodic*>(dimg + o_desc), dimg + tab[0], nullptr};
   }
 };
 

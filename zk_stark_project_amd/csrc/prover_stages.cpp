@@ -203,18 +203,25 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
     // Strided assertions append [columns | values | sequence descriptors | sequence tables]:
     // per sequence the k coefficients of V_j, interpolated over <w_k>, twisted by
     // w_n^(-first i) and multiplied by n (the coefficient layout k_strided_combine writes).
+    // With public inputs (zkp_air_register_params; pr is the instance) the image holds no value of
+    // pub and is shared by every instance of the id: the sequence tables section holds the concrete
+    // sequences' raw values, a section of ProgPubSeq descriptors follows it, and the periodic
+    // assertions' values and the sequences' coefficients are per-proof device arrays (below).
+    const bool params = pr.num_pub != 0;
     const std::vector<airp::Strided>& sv = pr.strided;
     const size_t S = sv.size();
     size_t nseq = 0, seq_felts = 0;
     for (const airp::Strided& a : sv)
-      if (a.sequence()) nseq++, seq_felts += a.values.size();
+      if (a.sequence()) nseq++, seq_felts += a.nvals;
     const size_t o_col = lay.end(), o_scol = o_col + (pr.a_col.size() + 3) / 4, o_sval = o_scol + (S + 3) / 4,
-                 o_sdesc = o_sval + S, o_stab = o_sdesc + (nseq + 1) / 2, total = o_stab + seq_felts;
+                 o_sdesc = o_sval + S, o_stab = o_sdesc + (nseq + 1) / 2, o_pseq = o_stab + seq_felts,
+                 total = o_pseq + (params ? nseq : 0);
     felt* dimg = ctx->buf<felt>("prog_image", total);
     std::vector<felt>& img = ctx->host_cache["prog_image"];  // kept: a large image is copied from it asynchronously
     std::vector<felt>& tag = ctx->host_cache["prog_image_tag"];
     const felt want[2] = {make((uint64_t)air.id, logn), make(logce, total)};
     if (tag.size() != 2 || !eq(tag[0], want[0]) || !eq(tag[1], want[1])) {
+      const auto img_t0 = std::chrono::steady_clock::now();
       tag.clear();
       img.assign(total, zero());
       lay.write(img.data());
@@ -228,11 +235,21 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
       }
       uint32_t* scol = reinterpret_cast<uint32_t*>(img.data() + o_scol);
       ProgSeq* sdesc = reinterpret_cast<ProgSeq*>(img.data() + o_sdesc);
+      ProgPubSeq* pseq = reinterpret_cast<ProgPubSeq*>(img.data() + o_pseq);
       size_t soff = 0, q = 0;
       for (size_t j = 0; j < S; j++) {
         scol[j] = sv[j].col;
-        img[o_sval + j] = sv[j].val;
+        img[o_sval + j] = params ? zero() : sv[j].val;
         if (!sv[j].sequence()) continue;
+        if (params) {
+          const uint32_t k = sv[j].nvals;
+          if (sv[j].pub < 0) memcpy(img.data() + o_stab + soff, sv[j].values.data(), (size_t)k * 16);
+          pseq[q] = ProgPubSeq{(uint32_t)soff, ilog2(k), (uint32_t)sv[j].first,
+                               sv[j].pub < 0 ? 0u : (uint32_t)sv[j].pub + 1};
+          sdesc[q++] = ProgSeq{(uint32_t)j, (uint32_t)soff};
+          soff += k;
+          continue;
+        }
         std::vector<felt> pc = sv[j].values;
         host_interpolate(pc, one());
         const felt tw = inv(pow_u64(wn, sv[j].first));
@@ -246,10 +263,66 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
       }
       ctx->upload(dimg, img.data(), total * 16);
       tag.assign(want, want + 2);
+      if (pf.enabled) {  // the image's host cost: periodic tables, sequence interpolation, staging
+        auto& hs = ctx->stats["host_prog_image"];
+        hs.launches += 1;
+        hs.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - img_t0).count();
+        hs.bytes += (double)total * 16;
+      }
     }
     ec.zinv = dz;
     ProgEvalArgs pa{};
     pa.code = lay.code(dimg);
+    const felt* dsval = dimg + o_sval;
+    const felt* dstab = dimg + o_stab;
+    if (params) {
+      // the instance, once per proof on the proof's stream: the pub table (through the pinned
+      // ring, or above its 1 MiB an asynchronous copy from the instance's own vector, which the
+      // proof's AirDesc keeps alive), the strided assertions' values, and every sequence
+      // interpolated on the device: gather, one inverse NTT per group, twist
+      felt* dpub = ctx->buf<felt>("prog_pub", pr.num_pub);
+      ctx->upload(dpub, pr.pub.data(), (size_t)pr.num_pub * 16);
+      pa.code.pub = dpub;
+      if (S) {
+        std::vector<felt> sval(S);
+        for (size_t j = 0; j < S; j++) sval[j] = sv[j].val;  // zero for a sequence
+        felt* d = ctx->buf<felt>("prog_sval", S);
+        ctx->upload(d, sval.data(), S * 16);
+        dsval = d;
+      }
+      if (nseq) {
+        felt* vals = ctx->buf<felt>("prog_seq_vals", seq_felts);
+        felt* ntt = ctx->buf<felt>("prog_seq_ntt", seq_felts);
+        felt* tab = ctx->buf<felt>("prog_seq_tab", seq_felts);
+        ProgPubSeqArgs ga{};
+        ga.nseq = (uint32_t)nseq;
+        ga.logn = logn;
+        ga.desc = reinterpret_cast<const ProgPubSeq*>(dimg + o_pseq);
+        ga.pub = dpub;
+        ga.raw = dimg + o_stab;
+        ga.itwn = ctx->itws(logN) + ((n >> 1) - 1);
+        uint64_t maxk = 1;
+        for (const airp::Strided& a : sv) maxk = std::max<uint64_t>(maxk, a.nvals);
+        launch_prog_seq_gather(pf, st, ga, maxk, vals);
+        // the sequences of one group are consecutive and share k: one batched transform each
+        size_t off = 0;
+        for (size_t j = 0; j < S;) {
+          size_t e = j, cnt = 0;
+          while (e < S && sv[e].stride == sv[j].stride && sv[e].first == sv[j].first) cnt += sv[e++].sequence();
+          const uint64_t k = n / sv[j].stride;
+          if (cnt && k > 1) {
+            NttBatch ib{vals + off, ntt + off, nullptr, k, k, 1, 1, (uint32_t)cnt};
+            launch_ntt(pf, st, ib, ilog2(k), false, ctx->itws(logN), logN);
+          } else if (cnt) {
+            HIP_CHECK(hipMemcpyAsync(ntt + off, vals + off, cnt * 16, hipMemcpyDeviceToDevice, st));
+          }
+          off += cnt * k;
+          j = e;
+        }
+        launch_prog_seq_twist(pf, st, ga, maxk, ntt, tab);
+        dstab = tab;
+      }
+    }
     pa.num_t = pr.num_t;
     pa.a_col = reinterpret_cast<const uint32_t*>(dimg + o_col);
     pa.cc = dt_cc;
@@ -276,10 +349,10 @@ void constraint_eval(zkp_ctx* ctx, const AirDesc& air, uint32_t logn, uint32_t l
     ProgStridedArgs sa{};
     ProgSeqArgs qa{};
     sa.col = reinterpret_cast<const uint32_t*>(dimg + o_scol);
-    sa.val = dimg + o_sval;
+    sa.val = dsval;
     sa.cc = qa.cc = dt_cc + pr.num_t + pr.a_col.size();
     qa.desc = reinterpret_cast<const ProgSeq*>(dimg + o_sdesc);
-    qa.tab = dimg + o_stab;
+    qa.tab = dstab;
     int wslot[PROG_MAX_STRIDED_GROUPS] = {-1, -1, -1, -1};  // the group's column of W, if it holds a sequence
     uint32_t seqs = 0;
     for (size_t j = 0; j < S; j++) {

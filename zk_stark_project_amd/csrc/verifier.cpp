@@ -435,7 +435,10 @@ int verify_impl(int air_id, const uint8_t* proof, uint64_t len, const zkp_felt* 
 extern "C" int zkp_verify(zkp_air_id air, const uint8_t* proof, uint64_t proof_len, const zkp_felt* pub_elems,
                           uint64_t n_pub, const zkp_proof_options* acceptable) {
   try {
-    return verify_impl((int)air, proof, proof_len, pub_elems, n_pub, acceptable);
+    // a registered id (>= 16) is outside the enumerators' range: read it as the int the C caller passed
+    int air_id;
+    memcpy(&air_id, &air, sizeof air_id);
+    return verify_impl(air_id, proof, proof_len, pub_elems, n_pub, acceptable);
   } catch (const VFail& f) {
     return f.code;
   } catch (const ZkpFail&) {
@@ -445,20 +448,98 @@ extern "C" int zkp_verify(zkp_air_id air, const uint8_t* proof, uint64_t proof_l
   }
 }
 
+// ---- caller-defined AIRs: the table of constraint programs (air_program.hpp). Host-only,
+// beside the verifier so that a host build without the device code has them.
+extern "C" int zkp_air_register(const zkp_air_program* program, int* air_id) {
+  return zkp_air_register_strided(program, nullptr, 0, air_id);
+}
+
+extern "C" int zkp_air_register_strided(const zkp_air_program* program, const zkp_air_strided_assertion* strided,
+                                        uint32_t num_strided, int* air_id) {
+  std::string& err = airp::last_error();
+  err.clear();
+  try {
+    if (!air_id) {
+      err = "air_id: null";
+      return ZKP_ERR_ARGUMENT;
+    }
+    auto p = std::make_shared<airp::Program>();
+    err = airp::validate(program, *p);
+    if (err.empty()) err = airp::validate_strided(strided, num_strided, *p);
+    if (!err.empty()) return ZKP_ERR_ARGUMENT;
+    *air_id = airp::insert(std::move(p));
+    return ZKP_OK;
+  } catch (const std::bad_alloc&) {
+    return ZKP_ERR_OOM;
+  } catch (...) {
+    return ZKP_ERR_ARGUMENT;
+  }
+}
+
+extern "C" int zkp_air_register_params(const zkp_air_program* program, const zkp_air_strided_assertion* strided,
+                            uint32_t num_strided, uint32_t num_pub, const zkp_air_binding* bindings,
+                            uint32_t num_bindings, int* air_id) {
+  std::string& err = airp::last_error();
+  err.clear();
+  try {
+    if (!air_id) {
+      err = "air_id: null";
+      return ZKP_ERR_ARGUMENT;
+    }
+    if (num_pub < 1 || num_pub > ZKP_AIR_MAX_PUB) {
+      err = "num_pub: must be 1..2^19";
+      return ZKP_ERR_ARGUMENT;
+    }
+    auto p = std::make_shared<airp::Program>();
+    std::vector<uint32_t> order;
+    std::vector<int64_t> single, bound;
+    err = airp::validate(program, *p, num_pub, &order);
+    if (err.empty()) err = airp::validate_bindings(program, strided, num_strided, num_pub, bindings, num_bindings, single, bound);
+    if (err.empty()) err = airp::validate_strided(strided, num_strided, *p, &bound);
+    if (!err.empty()) return ZKP_ERR_ARGUMENT;
+    for (size_t k = 0; k < order.size(); k++) p->a_pub[k] = single[order[k]];
+    *air_id = airp::insert(std::move(p));
+    return ZKP_OK;
+  } catch (const std::bad_alloc&) {
+    return ZKP_ERR_OOM;
+  } catch (...) {
+    return ZKP_ERR_ARGUMENT;
+  }
+}
+
+extern "C" int zkp_air_unregister(int air_id) {
+  std::string& err = airp::last_error();
+  err.clear();
+  if (airp::erase(air_id)) return ZKP_OK;
+  err = "air_id: not a registered id";
+  return ZKP_ERR_ARGUMENT;
+}
+
+extern "C" const char* zkp_air_last_error(void) { return airp::last_error().c_str(); }
+
 // Host trace validation for a registered constraint program (include/zkp.h): the
 // interpreter of air_program.hpp on every frame (rows r, r+1; periodic column p at
 // row r is its value r mod cycle), then the assertions in their stored order.
 extern "C" int zkp_air_check_trace(int air_id, const zkp_felt* trace_cols, uint32_t width, uint64_t n,
                                    uint64_t* bad_row, uint32_t* bad_constraint, uint32_t* bad_assertion) {
-  if (!trace_cols || !bad_row || !bad_constraint || !bad_assertion) return ZKP_ERR_ARGUMENT;
+  return zkp_air_check_trace_pub(air_id, nullptr, 0, trace_cols, width, n, bad_row, bad_constraint, bad_assertion);
+}
+
+extern "C" int zkp_air_check_trace_pub(int air_id, const zkp_felt* pub_elems, uint64_t n_pub,
+                                       const zkp_felt* trace_cols, uint32_t width, uint64_t n, uint64_t* bad_row,
+                                       uint32_t* bad_constraint, uint32_t* bad_assertion) {
+  if (!trace_cols || !bad_row || !bad_constraint || !bad_assertion || (n_pub && !pub_elems)) return ZKP_ERR_ARGUMENT;
   if (air_id == ZKP_AIR_MIMC || air_id == ZKP_AIR_GLOBAL_UPDATE || air_id == ZKP_AIR_TRAINING_UPDATE)
     return ZKP_ERR_UNSUPPORTED_AIR;
   if (n < 8 || (n & (n - 1)) || width == 0 || width > 255) return ZKP_ERR_TRACE_SHAPE;
   try {
     AirDesc air;
-    const int rc = build_air(air, air_id, width, n, {});
+    std::vector<felt> pub(n_pub);
+    for (uint64_t i = 0; i < n_pub; i++) pub[i] = make(pub_elems[i].lo, pub_elems[i].hi);
+    const int rc = build_air(air, air_id, width, n, pub);
     if (rc) return rc;
     const airp::Program& pr = *air.prog;
+    if (!pr.num_pub && n_pub) return ZKP_ERR_PUB_INPUTS;  // an id without public inputs takes none here
     *bad_row = UINT64_MAX;
     *bad_constraint = UINT32_MAX;
     *bad_assertion = UINT32_MAX;

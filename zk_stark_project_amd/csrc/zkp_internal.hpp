@@ -308,6 +308,7 @@ struct ProgCode {
   const felt* consts;    // device: the constant pool
   const ProgPeriodic* per_desc;  // device: one per periodic column
   const felt* per_tab;   // device: the periodic columns' tables
+  const felt* pub;       // device: the instance's public inputs (ZKP_SRC_PUB operands; uniform loads), or null
 };
 // A program over the CE domain (k_eval_program):
 // the op stream runs once per CE point, T = sum_i cc[i] * t_i over Z_T, then per group
@@ -365,6 +366,25 @@ struct ProgSeqArgs {
   const felt* cc;        // device: the coefficient of the first strided assertion
 };
 void launch_strided_combine(Prof& prof, hipStream_t s, const ProgSeqArgs& a, uint32_t logn, felt* out);
+// The sequences of a program with public inputs, interpolated per proof on the device. Sequence d
+// holds k = 2^logk values at `off` in three buffers of the same layout:
+//   gather: vals[off + i] = pub[pub1 - 1 + i] (bound), or raw[off + i] (a concrete sequence's values)
+//   launch_ntt (natural in, bit-reversed out, inverse table): ntt[off + p] = k * c_rev(p)
+//   twist:  tab[off + i] = ntt[off + rev(i)] * (n / k) * w_n^(-first i), what k_strided_combine reads
+struct ProgPubSeq {
+  uint32_t off, logk, first, pub1;
+};
+struct ProgPubSeqArgs {
+  uint32_t nseq, logn;
+  const ProgPubSeq* desc;  // device (uniform loads)
+  const felt* pub;         // device: the pub table
+  const felt* raw;         // device: the concrete sequences' values (the image)
+  const felt* itwn;        // device: w_n^-j, j < n/2 (inverse twiddle level logn - 1)
+};
+// maxk: the longest sequence (the grid covers it for every sequence)
+void launch_prog_seq_gather(Prof& prof, hipStream_t s, const ProgPubSeqArgs& a, uint64_t maxk, felt* vals);
+void launch_prog_seq_twist(Prof& prof, hipStream_t s, const ProgPubSeqArgs& a, uint64_t maxk, const felt* ntt,
+                           felt* tab);
 
 // The natural trace T (column-major, width x n) against a registered program
 // (k_check_program; zkp_air_check_trace_device): one frame per thread, then the
@@ -374,7 +394,7 @@ void launch_strided_combine(Prof& prof, hipStream_t s, const ProgSeqArgs& a, uin
 struct ProgStridedCells {
   uint32_t col, first, stride, count;  // cells T[col][first + stride * i], i < count = n / stride
   uint32_t blk0, voff;   // first of its blocks among the strided ones; values at svals + voff, or 0xffffffff: val
-  uint32_t pad[2];
+  uint32_t pub1, pad;    // pub1 != 0 (a bound assertion): pub[pub1 - 1] periodic, pub[pub1 - 1 + i] a sequence's cell i
   felt val;
 };
 struct ProgCheckArgs {
