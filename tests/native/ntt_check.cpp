@@ -3,25 +3,70 @@
 // (TEST ONLY; run by tests/test_gpu_ntt.py). The NTT rounds take every product
 // and sum as canonical and redo a round with the exact forms when a lane saw a
 // carry past 2^128 or a top limb 0xffffffff. Random data reaches
-// that branch about once per 2^26 operations, so the parity tests never do;
-// here the inputs put p - 1 against small values so the first stages' sums land
-// in [p, 2^128) in every lane (dense) or in one lane of many (sparse), for the DIF
-// (natural in, bit-reversed out) and DIT (bit-reversed in, natural out, with and
-// without the coset scale) passes, 2^11 .. 2^21, several batches: 45 cases, which
-// between them launch every k_ntt8 instantiation of ntt.hip's ZKP_NTT8_KERNELS and
-// the one-, two- and three-pass plans. Every output is compared with a naive
-// O(n^2) host DFT (2^11) or the host radix-2 NTT.
-// Prints one line per case and exits non-zero on any mismatch.
+// that branch about once per 2^32 operations, so the parity tests never do on purpose.
+//
+// Built twice from this source (tests/native/Makefile): ntt_check links ntt.hip as the
+// library compiles it and shows that the values are right; ntt_check_count links it with
+// ZKP_COUNT_REDO, whose per-site wave counters (slot 0: the staged coset-scale reload,
+// slot 1 + r: register round r) show that each case reached the redo it was built for,
+// and fails a case whose targeted site counted 0.
+//
+// Groups (ntt_check [group ...]; none = all):
+//   whole     the p - 1 / small-value patterns at the transform's input, in place, 2^11 ..
+//             2^21, DIF and DIT with and without a coset scale: 45 cases, every k_ntt8
+//             instantiation launched, the one-, two- and three-pass plans
+//   pass-dit, pass-dif, pass-9
+//             every (DIT, threads, K, SMALL) that ntt_plan can ask for, at the smallest
+//             logn and batch count that selects it, launched alone (only_pass); for every
+//             stage s of the pass the state ENTERING s is crafted (below) and carried back
+//             through the inverse butterflies of the pass's earlier stages to its input;
+//             every output is compared with the host's radix-2 stages [s0, s0 + K) of that
+//             input. pass-9 holds the 9-stage passes (2^20, 1 and 8 arrays), whose sweep is
+//             thinned to each round's first stage and one mid-round stage.
+//   lde       the prover's LDE launch: DIT, out of place, src_div = scale_mod = B cosets of
+//             one coefficient row, batches = columns * B, scale rows, table of n * B points;
+//             B in {2, 8, 16}, 2^11 .. 2^13 (batch-major grid) and 2^14, 2^17 (tile_major);
+//             the source is target * scale^-1 for one coset per column, so the scale product
+//             itself lands on p - 1 (dense, sparse), on sum-rare values (sum2) or is an alias
+//             whose fast value is wrong without the exact reload (prod-alias)
+//   forms     the interpolation launch (DIF, out of place, inverse table of the larger
+//             domain), a DIF with a scale, and the sequence launch (DIF of k points, strides
+//             k, table of a domain 2, 2^7 or 2^12 times larger, k = 2 .. 2^12)
+//   radix2    2^1 .. 2^10 (k_ntt_pass, branching mul / add: values only): the LDE launch
+//             with B in {2, 8, 128} and the interpolation launch
+//   big       2^22 and 2^23 (three passes: 6+8+8, 8+8+7), both directions, 2 arrays
+//
+// Patterns at a stage (x, y its butterfly's operands, t = w * y for DIT):
+//   dense / sparse  x = p - 1 against t (DIT) or y (DIF) in [1, 2^32): the sum lies in
+//                   [p, 2^128), top limb 0xffffffff; every lane, or one butterfly in 97
+//   sum2            x = 2^127 + a, t or y = 2^127 - 2^40 - a': the sum lies in [p, 2^128)
+//                   and no operand has a top limb 0xffffffff
+//   prod-top        the twiddle product's residue has top limb 0xffffffff
+//   prod-alias      the twiddle product's residue is below 2^64: the unreduced value is the
+//                   residue or the residue + p, which for a residue < 2^128 - p has top limb
+//                   0xffffffff and for one >= 2^128 - p carries past 2^128 (odd butterflies
+//                   take the first kind, even ones the second)
+// Every reference is the portable host arithmetic (felt.hpp): stage by stage for the pass
+// cases, whole transforms by the same stages, tied at start-up to host_ntt (host_stark.hpp)
+// and to a naive O(n^2) DFT, which is also the reference of the smallest sizes.
+// Prints one line per case and exits non-zero on any mismatch (or uncounted target).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <map>
 #include <stdexcept>
 #include <string>
+#include <thread>
+#include <tuple>
 #include <vector>
 
 #include "../../zk_stark_project_amd/csrc/zkp_internal.hpp"
 #include "../../zk_stark_project_amd/csrc/host_stark.hpp"
+#include "../../zk_stark_project_amd/csrc/ntt_plan.hpp"
 
 using namespace fp;
 using namespace zkh;
@@ -31,6 +76,15 @@ hipEvent_t Prof::get_event() { return nullptr; }
 void Prof::begin(const char*, hipStream_t, double) {}
 void Prof::end(hipStream_t) {}
 void launch_fail(int code, const char* what) { throw std::runtime_error(std::string(what) + " " + std::to_string(code)); }
+
+#ifdef ZKP_COUNT_REDO
+void zkp_ntt_redo_waves_take(unsigned long long out[5]);  // ntt.hip (ZKP_COUNT_REDO)
+int zkp_ntt_round_bits(int K, int r);
+static const bool COUNTING = true;
+#else
+static void zkp_ntt_redo_waves_take(unsigned long long out[5]) { memset(out, 0, 5 * sizeof out[0]); }
+static const bool COUNTING = false;
+#endif
 
 #define CK(x)                                                                   \
   do {                                                                          \
@@ -111,13 +165,240 @@ static std::vector<felt> naive(const std::vector<felt>& in, uint32_t logn, bool 
   return out;
 }
 
-int main() {
-  setvbuf(stdout, NULL, _IONBF, 0);
-  hipStream_t st;
-  CK(hipStreamCreate(&st));
-  Prof pf;
-  const felt pm1 = make(0xffffd30000000000ull, 0xffffffffffffffffull);  // p - 1
-  int bad = 0, cases = 0;
+static hipStream_t st;
+static Prof pf;
+static int bad = 0, cases = 0;
+static const felt PM1 = make(0xffffd30000000000ull, 0xffffffffffffffffull);  // p - 1
+
+// ------------------------------------------------------------ host helpers
+// at most 16 host threads
+static unsigned nthreads() {
+  const unsigned h = std::thread::hardware_concurrency();
+  return h == 0 ? 4 : (h > 16 ? 16 : h);
+}
+template <class F>
+static void par_for(size_t n, F f) {
+  const unsigned T = nthreads();
+  if (n < 8192 || T == 1) {
+    f((size_t)0, n);
+    return;
+  }
+  std::vector<std::thread> th;
+  const size_t chunk = (n + T - 1) / T;
+  for (unsigned t = 0; t < T; t++) {
+    const size_t b = (size_t)t * chunk, e = std::min(n, b + chunk);
+    if (b >= e) break;
+    th.emplace_back([=, &f] { f(b, e); });
+  }
+  for (auto& x : th) x.join();
+}
+
+// counter-based random values (any thread can draw element i of stream `seed`)
+static uint64_t mix(uint64_t z) {
+  z += 0x9e3779b97f4a7c15ull;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+static uint64_t hash2(uint64_t seed, uint64_t i) { return mix(mix(seed) ^ (i * 0xd6e8feb86659fd93ull)); }
+static felt hfelt(uint64_t seed, uint64_t i) {
+  felt v = make(hash2(seed, 2 * i), hash2(seed, 2 * i + 1));
+  if (ge_p(v)) v.hi &= 0x7fffffffffffffffull;
+  return v;
+}
+static void fill_random(std::vector<felt>& v, uint64_t seed) {
+  par_for(v.size(), [&](size_t b, size_t e) {
+    for (size_t i = b; i < e; i++) v[i] = hfelt(seed, i);
+  });
+}
+
+// the shared twiddle tables (stage-major; a smaller domain's table is a prefix), host + device
+static struct {
+  uint32_t logN = 0;
+  std::vector<felt> f, i;
+  felt *df = nullptr, *di = nullptr;
+} TB;
+static void need_tables(uint32_t logN) {
+  if (TB.logN >= logN) return;
+  if (TB.df) { CK(hipFree(TB.df)); CK(hipFree(TB.di)); }
+  TB.logN = logN;
+  TB.f.assign((size_t)1 << logN, zero());
+  TB.i.assign((size_t)1 << logN, zero());
+  for (uint32_t lev = 0; lev < logN; lev++) {
+    const felt w = root_of_unity(lev + 1), wi = inv(w);
+    const size_t base = ((size_t)1 << lev) - 1;
+    par_for((size_t)1 << lev, [&](size_t b, size_t e) {
+      felt a = pow_u64(w, b), ai = pow_u64(wi, b);
+      for (size_t j = b; j < e; j++) {
+        TB.f[base + j] = a;
+        TB.i[base + j] = ai;
+        a = mul(a, w);
+        ai = mul(ai, wi);
+      }
+    });
+  }
+  CK(hipMalloc(&TB.df, TB.f.size() * 16));
+  CK(hipMalloc(&TB.di, TB.i.size() * 16));
+  CK(hipMemcpy(TB.df, TB.f.data(), TB.f.size() * 16, hipMemcpyHostToDevice));
+  CK(hipMemcpy(TB.di, TB.i.data(), TB.i.size() * 16, hipMemcpyHostToDevice));
+}
+
+// device buffers that only grow
+struct DevBuf {
+  felt* p = nullptr;
+  size_t cap = 0;
+  felt* get(size_t count) {
+    if (count > cap) {
+      if (p) CK(hipFree(p));
+      CK(hipMalloc(&p, count * 16));
+      cap = count;
+    }
+    return p;
+  }
+};
+static DevBuf DSRC, DDST, DSCALE;
+
+// Radix-2 stage s of launch_ntt's transforms over `arrays` arrays of 2^logn (the device's stage
+// order and twiddles: DIT pairs i, i + 2^s, DIF pairs i, i + 2^(logn - 1 - s); twiddle level =
+// the pair bit, index = i's bits below it), or its inverse:
+//   DIT  x' = x + w y, y' = x - w y      <->  x = (x' + y') / 2, y = (x' - y') / (2 w)
+//   DIF  x' = x + y,   y' = (x - y) w    <->  d = y' / w, x = (x' + d) / 2, y = (x' - d) / 2
+static void host_stage(felt* v, size_t arrays, uint32_t logn, uint32_t s, bool dit, bool inverse) {
+  const uint32_t bit = dit ? s : logn - 1 - s;
+  const felt* tw = (dit != inverse ? TB.f.data() : TB.i.data()) + (((size_t)1 << bit) - 1);
+  const size_t half = (size_t)1 << (logn - 1), low = ((size_t)1 << bit) - 1;
+  const felt inv2 = inv(make(2, 0));
+  par_for(arrays * half, [&](size_t b, size_t e) {
+    for (size_t t = b; t < e; t++) {
+      const size_t u = t & (half - 1), j = u & low;
+      felt* a = v + ((t >> (logn - 1)) << logn);
+      felt& x = a[((u >> bit) << (bit + 1)) | j];
+      felt& y = a[((u >> bit) << (bit + 1)) | j | ((size_t)1 << bit)];
+      const felt w = tw[j];  // the stage's twiddle, or (inverse) its inverse
+      if (!inverse) {
+        if (dit) {
+          const felt tt = mul(y, w);
+          y = sub(x, tt);
+          x = add(x, tt);
+        } else {
+          const felt d = sub(x, y);
+          x = add(x, y);
+          y = mul(d, w);
+        }
+      } else if (dit) {
+        const felt sx = mul(add(x, y), inv2), d = mul(sub(x, y), inv2);
+        x = sx;
+        y = mul(d, w);
+      } else {
+        const felt d = mul(y, w);
+        const felt sx = mul(add(x, d), inv2);
+        y = mul(sub(x, d), inv2);
+        x = sx;
+      }
+    }
+  });
+}
+static void host_full(felt* v, size_t arrays, uint32_t logn, bool dit) {
+  for (uint32_t s = 0; s < logn; s++) host_stage(v, arrays, logn, s, dit, false);
+}
+
+enum Pat { DENSE, SPARSE, SUM2, PROD_TOP, PROD_ALIAS, NPAT };
+static const char* PAT_NAME[NPAT] = {"dense", "sparse", "sum2", "prod-top", "prod-alias"};
+
+// Overwrite the butterflies of stage s in the state v ENTERING it with the pattern (see the
+// file comment); butterflies the pattern leaves alone keep v's values.
+static void craft(felt* v, size_t arrays, uint32_t logn, uint32_t s, bool dit, Pat pat, uint64_t seed) {
+  const uint32_t bit = dit ? s : logn - 1 - s;
+  const felt* twi = (dit ? TB.i.data() : TB.f.data()) + (((size_t)1 << bit) - 1);  // inverse twiddles
+  const size_t half = (size_t)1 << (logn - 1), low = ((size_t)1 << bit) - 1;
+  par_for(arrays * half, [&](size_t b, size_t e) {
+    for (size_t t = b; t < e; t++) {
+      if (pat == SPARSE && t % 97 != 0) continue;
+      const size_t u = t & (half - 1), j = u & low;
+      felt* a = v + ((t >> (logn - 1)) << logn);
+      felt& x = a[((u >> bit) << (bit + 1)) | j];
+      felt& y = a[((u >> bit) << (bit + 1)) | j | ((size_t)1 << bit)];
+      const uint64_t h = hash2(seed ^ 0x5bd1e995u, t), h2 = hash2(seed ^ 0x1b873593u, t);
+      const felt wi = twi[j];
+      felt T;  // DIT: w * y; DIF: y (sums) or (x - y) * w (products)
+      switch (pat) {
+        case DENSE:
+        case SPARSE:
+          x = PM1;
+          T = make((h & 0xffffffffull) | 1ull, 0);
+          break;
+        case SUM2:
+          x = make(h & 0xffffffffull, 0x8000000000000000ull);
+          T = make(0ull - (1ull << 40) - (h2 & 0xffffffffull), 0x7fffffffffffffffull);
+          break;
+        case PROD_TOP:
+          T = make(h, 0xffffffff00000000ull | (h2 >> 33));
+          break;
+        default:  // PROD_ALIAS
+          T = (t & 1) ? make(h % C, 0) : make(C + (h >> 4), 0);
+          break;
+      }
+      if (pat == PROD_TOP || pat == PROD_ALIAS) {
+        if (dit) y = mul(T, wi);
+        else y = sub(x, mul(T, wi));
+      } else {
+        y = dit ? mul(T, wi) : T;
+      }
+    }
+  });
+}
+
+// rounds of a K-stage pass (ntt.hip NttRounds: <= 3 stages each, larger first); checked
+// against ntt.hip's own under ZKP_COUNT_REDO
+static int round_count(int K) { return (K + 2) / 3; }
+static int round_bits(int K, int r) {
+  const int n = round_count(K);
+  int rem = K;
+  for (int i = 0; i <= r; i++) {
+    const int left = n - i;
+    int b = (rem + left - 1) / left;
+    if (b > 3) b = 3;
+    if (i == r) return b;
+    rem -= b;
+  }
+  return 0;
+}
+static int round_of_stage(int K, int ls) {
+  for (int r = 0, c = 0; r < round_count(K); r++) {
+    c += round_bits(K, r);
+    if (ls < c) return r;
+  }
+  return -1;
+}
+
+static size_t count_mismatch(const felt* want, const felt* got, size_t count) {
+  size_t m = 0;
+  for (size_t i = 0; i < count; i++) m += !eq(want[i], got[i]);
+  return m;
+}
+
+static std::string counts_str(const unsigned long long c[5]) {
+  char buf[128];
+  snprintf(buf, sizeof buf, "redo waves [scale %llu | rounds %llu %llu %llu %llu]", c[0], c[1], c[2], c[3], c[4]);
+  return COUNTING ? std::string(buf) : std::string();
+}
+
+// a case's verdict: mismatches, and (counting build) the sites that had to count
+static void verdict(const std::string& name, size_t mism, const unsigned long long c[5], unsigned need_sites,
+                    const char* extra = "") {
+  bool uncounted = false;
+  if (COUNTING)
+    for (int sidx = 0; sidx < 5; sidx++)
+      if ((need_sites >> sidx & 1) && c[sidx] == 0) uncounted = true;
+  cases++;
+  if (mism || uncounted) bad++;
+  printf("%s: %s%s%s %s\n", name.c_str(), mism ? "MISMATCH" : "ok", uncounted ? " TARGET SITE NOT REACHED" : "", extra,
+         counts_str(c).c_str());
+}
+
+// ------------------------------------------------------------ group: whole
+static void group_whole() {
+  const felt pm1 = PM1;
   // all three patterns at 2^11 (one pass), 2^13 (6 + 7) and 2^18 (11 + 7); the dense pattern
   // (both directions, scaled DIT) for the kernels those leave out: 2^12 (6 + 6), 2^16 (8 + 8),
   // 2^19-2^20 (11 + 8/9; 9 stages in 512-thread blocks from 8 batches) and 2^21 (6 + 8 + 7)
@@ -145,7 +426,10 @@ int main() {
               // the first stage's partner of i: i + n/2 (DIF), i ^ 1 in storage order (DIT)
               const bool lo_half = dit ? (i & 1) == 0 : i < n / 2;
               if (pattern == 0) v = lo_half ? pm1 : make(rnd() & 0xffffffffull, 0);            // dense: every lane
-              if (pattern == 1 && (i % 97) < 2) v = lo_half ? pm1 : make(rnd() & 0xffff, 0);   // sparse lanes
+              // sparse lanes: both partners of one butterfly in 97 (chosen by i alone, the DIF
+              // partners i, i + n/2 never both took the pattern and no round was redone)
+              const uint64_t pair = dit ? i >> 1 : i & (n / 2 - 1);
+              if (pattern == 1 && pair % 97 == 0) v = lo_half ? pm1 : make(rnd() & 0xffff, 0);
               if (pattern == 2 && (i % 5) == 0) v = sub(pm1, make(rnd() & 0xff, 0));          // near p, random partners
               h[(size_t)b * n + i] = v;
             }
@@ -162,25 +446,380 @@ int main() {
           CK(hipStreamSynchronize(st));
           std::vector<felt> g(h.size());
           CK(hipMemcpy(g.data(), d, g.size() * 16, hipMemcpyDeviceToHost));
-          int mism = 0;
-          for (uint32_t b = 0; b < batches; b++) {
-            std::vector<felt> in(h.begin() + (size_t)b * n, h.begin() + (size_t)(b + 1) * n);
-            if (scaled)
-              for (uint64_t i = 0; i < n; i++) in[i] = mul(in[i], S[(size_t)(b % 2) * n + i]);
-            const std::vector<felt> want = logn == 11 ? naive(in, logn, dit != 0) : host_ref(in, logn, dit != 0);
-            for (uint64_t i = 0; i < n; i++)
-              if (!eq(want[i], g[(size_t)b * n + i])) mism++;
-          }
-          cases++;
-          if (mism) bad++;
-          printf("n=2^%u %s pattern=%d scale=%d batches=%u: %s\n", logn, dit ? "DIT" : "DIF", pattern, scaled, batches,
-                 mism ? "MISMATCH" : "ok");
+          std::vector<size_t> miss(batches, 0);
+          std::vector<std::thread> th;  // one host transform per batch (<= 8)
+          for (uint32_t b = 0; b < batches; b++)
+            th.emplace_back([&, b] {
+              std::vector<felt> in(h.begin() + (size_t)b * n, h.begin() + (size_t)(b + 1) * n);
+              if (scaled)
+                for (uint64_t i = 0; i < n; i++) in[i] = mul(in[i], S[(size_t)(b % 2) * n + i]);
+              const std::vector<felt> want = logn == 11 ? naive(in, logn, dit != 0) : host_ref(in, logn, dit != 0);
+              miss[b] = count_mismatch(want.data(), g.data() + (size_t)b * n, n);
+            });
+          for (auto& x : th) x.join();
+          size_t mism = 0;
+          for (size_t m : miss) mism += m;
+          unsigned long long cnt[5];
+          zkp_ntt_redo_waves_take(cnt);
+          char name[128];
+          snprintf(name, sizeof name, "whole n=2^%u %s pattern=%d scale=%d batches=%u", logn, dit ? "DIT" : "DIF", pattern,
+                   scaled, batches);
+          // the dense and sparse patterns sit on the first stage: the first pass's round 0
+          // (a random scale takes most of the sparse pattern's few lanes away)
+          verdict(name, mism, cnt, pattern == 0 || (pattern == 1 && !scaled) ? 2u : 0u);
           CK(hipFree(d));
           if (ds) CK(hipFree(ds));
         }
     CK(hipFree(dtf));
     CK(hipFree(dti));
   }
-  printf("%d cases, %d mismatching\n", cases, bad);
+}
+
+// ------------------------------------------------------------ groups: pass-*
+// (dit, threads, K, small) -> where ntt_plan first selects it
+struct Inst {
+  bool dit;
+  uint32_t nt, K;
+  bool small;
+  uint32_t logn, batches, pass;
+};
+static std::vector<Inst> instantiations() {
+  std::map<std::tuple<bool, uint32_t, uint32_t, bool>, Inst> seen;
+  for (uint32_t logn = 11; logn <= 23; logn++)
+    for (uint32_t batches : {1u, 8u})
+      for (int dit = 1; dit >= 0; dit--) {
+        const NttPlan pl = ntt_plan(logn, dit != 0, batches);
+        for (uint32_t p = 0; p < pl.n; p++) {
+          const NttPass& ps = pl.pass[p];
+          const auto key = std::make_tuple(dit != 0, 1u << ps.lognt, ps.K, ps.small);
+          if (!seen.count(key)) seen[key] = Inst{dit != 0, 1u << ps.lognt, ps.K, ps.small, logn, batches, p};
+        }
+      }
+  std::vector<Inst> v;
+  for (const auto& kv : seen) v.push_back(kv.second);
+  return v;
+}
+
+// which: 0 = DIT passes of < 9 stages and the 11-stage ones, 1 = the DIF ones, 2 = 9 stages (2^20)
+static void group_pass(int which) {
+  need_tables(21);
+  int ninst = 0;
+  for (const Inst& in : instantiations()) {
+    const bool nine = in.K == 9;
+    if (which == 2 ? !nine : (nine || in.dit != (which == 0))) continue;
+    ninst++;
+    const uint32_t logn = in.logn, batches = in.batches, K = in.K;
+    const size_t n = (size_t)1 << logn, total = n * batches;
+    const NttPass ps = ntt_plan(logn, in.dit, batches).pass[in.pass];
+    const int nr = round_count((int)K);
+#ifdef ZKP_COUNT_REDO
+    for (int r = 0; r <= nr; r++)
+      if (zkp_ntt_round_bits((int)K, r) != (r < nr ? round_bits((int)K, r) : 0)) {
+        printf("round structure of K=%u differs from ntt.hip's\n", K);
+        bad++;
+      }
+#endif
+    // the sweep: every stage x every pattern; thinned for the large launches to each round's
+    // first stage (dense; sparse too in round 0) and its second stage (one other pattern each)
+    std::vector<std::pair<uint32_t, Pat>> sweep;
+    const bool thin = total >= ((size_t)1 << 20);
+    if (!thin) {
+      for (uint32_t ls = 0; ls < K; ls++)
+        for (int p = 0; p < NPAT; p++) sweep.push_back({ls, (Pat)p});
+    } else {
+      uint32_t ls0 = 0;
+      for (int r = 0; r < nr; ls0 += round_bits((int)K, r), r++) {
+        sweep.push_back({ls0, DENSE});
+        if (r == 0) sweep.push_back({ls0, SPARSE});
+        if (round_bits((int)K, r) > 1) sweep.push_back({ls0 + 1, (Pat)(SUM2 + r % 3)});
+      }
+    }
+    unsigned long long site_total[5] = {0, 0, 0, 0, 0};
+    std::vector<felt> A(total), in0(total), got(total);
+    felt* d = DDST.get(total);
+    for (const auto& sp : sweep) {
+      const uint32_t s = ps.s0 + sp.first;
+      const Pat pat = sp.second;
+      const uint32_t bit = in.dit ? s : logn - 1 - s;
+      if ((pat == PROD_TOP || pat == PROD_ALIAS) && bit == 0) continue;  // every twiddle is 1: no product
+      const uint64_t seed = ((uint64_t)logn << 40) ^ ((uint64_t)s << 32) ^ ((uint64_t)pat << 24) ^ (in.dit ? 1u : 0u) ^ (K << 8);
+      fill_random(A, seed);
+      craft(A.data(), batches, logn, s, in.dit, pat, seed);
+      in0 = A;
+      for (uint32_t q = s; q-- > ps.s0;) host_stage(in0.data(), batches, logn, q, in.dit, true);
+      CK(hipMemcpy(d, in0.data(), total * 16, hipMemcpyHostToDevice));
+      NttBatch nb{d, d, nullptr, n, n, 1, 1, batches};
+      launch_ntt(pf, st, nb, logn, in.dit, in.dit ? TB.df : TB.di, TB.logN, (int)in.pass);
+      CK(hipStreamSynchronize(st));
+      CK(hipMemcpy(got.data(), d, total * 16, hipMemcpyDeviceToHost));
+      // host: the pass's stages of the same input; on the way, the state entering s is the crafted one
+      size_t craft_miss = 0;
+      for (uint32_t q = ps.s0; q < ps.s0 + K; q++) {
+        if (q == s) craft_miss = count_mismatch(A.data(), in0.data(), total);
+        host_stage(in0.data(), batches, logn, q, in.dit, false);
+      }
+      const size_t mism = count_mismatch(in0.data(), got.data(), total);
+      unsigned long long cnt[5];
+      zkp_ntt_redo_waves_take(cnt);
+      for (int i = 0; i < 5; i++) site_total[i] += cnt[i];
+      const int r = round_of_stage((int)K, (int)sp.first);
+      char name[160];
+      snprintf(name, sizeof name, "pass %s nt=%u K=%u small=%d n=2^%u batches=%u pass=%u stage=%u (round %d) %s",
+               in.dit ? "DIT" : "DIF", in.nt, K, (int)in.small, logn, batches, in.pass, s, r, PAT_NAME[pat]);
+      verdict(name, mism + craft_miss, cnt, 1u << (1 + r), craft_miss ? " (host: crafted state not reproduced)" : "");
+    }
+    bool all = true;
+    for (int r = 0; r < nr; r++) all = all && site_total[1 + r] > 0;
+    if (COUNTING) {
+      printf("TABLE k_ntt8<%s, %u, %u, %s> 2^%u x %u pass %u: rounds", in.dit ? "DIT" : "DIF", in.nt, K,
+             in.small ? "SMALL" : "-", logn, batches, in.pass);
+      for (int r = 0; r < nr; r++) printf(" r%d(%d stages)=%llu", r, round_bits((int)K, r), site_total[1 + r]);
+      printf("%s\n", all ? "" : "  ROUND NEVER REDONE");
+      if (!all) bad++;
+    }
+  }
+  printf("pass group %d: %d instantiations\n", which, ninst);
+}
+
+// ------------------------------------------------------------ launch forms
+// per-element inverses of v (Montgomery's trick; v has no zero)
+static std::vector<felt> batch_inv(const std::vector<felt>& v) {
+  std::vector<felt> pre(v.size()), out(v.size());
+  felt acc = one();
+  for (size_t i = 0; i < v.size(); i++) {
+    pre[i] = acc;
+    acc = mul(acc, v[i]);
+  }
+  felt ia = inv(acc);
+  for (size_t i = v.size(); i-- > 0;) {
+    out[i] = mul(ia, pre[i]);
+    ia = mul(ia, v[i]);
+  }
+  return out;
+}
+
+// compare `arrays` device results with the host's transform of `want` (in place: want holds the
+// inputs after any scale); at the smallest sizes the first arrays also against the naive DFT
+static size_t check_whole(std::vector<felt>& want, const std::vector<felt>& got, size_t arrays, uint32_t logn, bool dit) {
+  const size_t n = (size_t)1 << logn;
+  size_t mism = 0;
+  if (logn <= 11) {
+    const size_t na = logn <= 8 ? arrays : std::min<size_t>(arrays, 4);
+    for (size_t b = 0; b < na; b++) {
+      const std::vector<felt> w = naive(std::vector<felt>(want.begin() + b * n, want.begin() + (b + 1) * n), logn, dit);
+      mism += count_mismatch(w.data(), got.data() + b * n, n);
+    }
+  }
+  host_full(want.data(), arrays, logn, dit);
+  return mism + count_mismatch(want.data(), got.data(), arrays * n);
+}
+
+// The prover's LDE launch. Column c targets coset jt(c): its coefficient row is
+// target * scale_row(jt)^-1, target carrying `pat` on the first DIT stage (partners i, i ^ 1).
+static void lde_case(uint32_t logn, uint32_t B, uint32_t cols, Pat pat, unsigned need_sites, const char* label) {
+  const size_t n = (size_t)1 << logn;
+  const uint32_t batches = cols * B, logB = ilog2(B);
+  need_tables(logn + logB);
+  const uint64_t seed = ((uint64_t)logn << 32) ^ (B << 8) ^ pat ^ 0x4c4445ull;
+  std::vector<felt> S(B * n), src(cols * n), want((size_t)batches * n), got((size_t)batches * n);
+  fill_random(S, seed + 1);
+  for (auto& x : S)
+    if (is_zero(x)) x = one();
+  fill_random(src, seed + 2);  // the targets first
+  craft(src.data(), cols, logn, 0, true, pat, seed);
+  std::string targets;
+  for (uint32_t c = 0; c < cols; c++) {
+    const uint32_t jt = (c * 5 + 1) % B;
+    targets += (c ? "," : "") + std::to_string(jt);
+    const std::vector<felt> si = batch_inv(std::vector<felt>(S.begin() + jt * n, S.begin() + (jt + 1) * n));
+    for (size_t i = 0; i < n; i++) src[c * n + i] = mul(src[c * n + i], si[i]);
+  }
+  par_for((size_t)batches * n, [&](size_t b, size_t e) {
+    for (size_t t = b; t < e; t++) {
+      const size_t bt = t >> logn, i = t & (n - 1);
+      want[t] = mul(src[(bt / B) * n + i], S[(bt % B) * n + i]);
+    }
+  });
+  felt *ds = DSRC.get(src.size()), *dd = DDST.get(got.size()), *dsc = DSCALE.get(S.size());
+  CK(hipMemcpy(ds, src.data(), src.size() * 16, hipMemcpyHostToDevice));
+  CK(hipMemcpy(dsc, S.data(), S.size() * 16, hipMemcpyHostToDevice));
+  CK(hipMemset(dd, 0xff, got.size() * 16));
+  NttBatch nb{ds, dd, dsc, n, n, B, B, batches};
+  launch_ntt(pf, st, nb, logn, true, TB.df, logn + logB);
+  CK(hipStreamSynchronize(st));
+  CK(hipMemcpy(got.data(), dd, got.size() * 16, hipMemcpyDeviceToHost));
+  const size_t mism = check_whole(want, got, batches, logn, true);
+  unsigned long long cnt[5];
+  zkp_ntt_redo_waves_take(cnt);
+  // launch_ntt's tile_major condition for the first pass (printed so that a plan change cannot
+  // silently move a case to the other grid order): below 2^11 there is no k_ntt8
+  bool tile_major = false;
+  if (logn >= 11) {
+    const NttPass ps = ntt_plan(logn, true, batches).pass[0];
+    tile_major = B > 1 && (((1u << (logn - ps.K)) >> ps.logT) % 8 == 0);
+  }
+  const bool expect_tm = logn >= 14;
+  char name[160];
+  snprintf(name, sizeof name, "%s n=2^%u B=%u cols=%u (cosets %s) %s tile_major=%d", label, logn, B, cols, targets.c_str(),
+           PAT_NAME[pat], (int)tile_major);
+  if (tile_major != expect_tm) {
+    printf("%s: the launch is on the other side of tile_major than this case is meant for\n", name);
+    bad++;
+  }
+  verdict(name, mism, cnt, logn >= 11 ? need_sites : 0u);
+}
+
+static void group_lde() {
+  for (uint32_t logn : {11u, 12u, 13u, 14u, 17u})
+    for (uint32_t B : {2u, 8u, 16u}) {
+      const uint32_t cols = B == 16 ? 2 : 3;
+      // the scale product lands on p - 1: the staged reload (slot 0) and the first round (slot 1)
+      lde_case(logn, B, cols, DENSE, 3u, "lde");
+      lde_case(logn, B, cols, SPARSE, 3u, "lde");
+      // sum-rare targets only: the first round's redo without a rare scale product
+      lde_case(logn, B, cols, SUM2, 2u, "lde");
+      // The products above land on canonical values, which the fast form already returns: they
+      // reach the reload but would come out right without it. Here every odd element's scale
+      // product is an alias (residue + p, or a carry past 2^128), so the fast value is wrong
+      // and only the exact reload puts the canonical one into LDS.
+      lde_case(logn, B, cols, PROD_ALIAS, 1u, "lde");
+    }
+}
+
+// DIF, out of place, `batches` arrays of their own, optionally scale rows (scale_mod 2); the
+// pattern on the first stage (rows i, i + n/2); inverse table of a 2^logN domain
+static void dif_case(uint32_t logn, uint32_t logN, uint32_t batches, Pat pat, bool scaled, const char* label) {
+  const size_t n = (size_t)1 << logn, total = n * batches;
+  need_tables(logN);
+  const uint64_t seed = ((uint64_t)logn << 32) ^ ((uint64_t)logN << 16) ^ (batches << 8) ^ pat ^ 0x444946ull;
+  std::vector<felt> src(total), want, got(total), S;
+  fill_random(src, seed);
+  craft(src.data(), batches, logn, 0, false, pat, seed);
+  want = src;
+  if (scaled) {
+    S.resize(2 * n);
+    fill_random(S, seed + 1);
+    for (auto& x : S)
+      if (is_zero(x)) x = one();
+    const std::vector<felt> si = batch_inv(S);
+    for (size_t t = 0; t < total; t++) src[t] = mul(want[t], si[((t >> logn) % 2) * n + (t & (n - 1))]);
+    for (size_t t = 0; t < total; t++) want[t] = mul(src[t], S[((t >> logn) % 2) * n + (t & (n - 1))]);
+  }
+  felt *ds = DSRC.get(total), *dd = DDST.get(total), *dsc = scaled ? DSCALE.get(S.size()) : nullptr;
+  CK(hipMemcpy(ds, src.data(), total * 16, hipMemcpyHostToDevice));
+  if (scaled) CK(hipMemcpy(dsc, S.data(), S.size() * 16, hipMemcpyHostToDevice));
+  CK(hipMemset(dd, 0xff, total * 16));
+  NttBatch nb{ds, dd, dsc, n, n, 1, scaled ? 2u : 1u, batches};
+  launch_ntt(pf, st, nb, logn, false, TB.di, logN);
+  CK(hipStreamSynchronize(st));
+  CK(hipMemcpy(got.data(), dd, total * 16, hipMemcpyDeviceToHost));
+  const size_t mism = check_whole(want, got, batches, logn, false);
+  unsigned long long cnt[5];
+  zkp_ntt_redo_waves_take(cnt);
+  char name[160];
+  snprintf(name, sizeof name, "%s n=2^%u table=2^%u batches=%u %s", label, logn, logN, batches, PAT_NAME[pat]);
+  verdict(name, mism, cnt, logn >= 11 ? 2u : 0u);  // k_ntt8: the first pass's round 0
+}
+
+static void group_forms() {
+  need_tables(24);  // the sequence launches' largest domain
+  for (uint32_t logn : {11u, 12u, 13u, 14u, 17u})
+    for (Pat pat : {DENSE, SPARSE, SUM2}) dif_case(logn, logn + 3, 3, pat, false, "interpolation");
+  dif_case(12, 13, 3, DENSE, true, "dif-with-scale");
+  for (uint32_t logk = 1; logk <= 12; logk++)
+    for (uint32_t batches : {1u, 3u})
+      for (uint32_t up : {1u, 7u, 12u}) dif_case(logk, logk + up, batches, logk % 2 ? DENSE : SUM2, false, "sequence");
+}
+
+static void group_radix2() {
+  for (uint32_t logn = 1; logn <= 10; logn++) {
+    for (uint32_t B : {2u, 8u, 128u}) lde_case(logn, B, 2, logn % 2 ? DENSE : SUM2, 0u, "radix2-lde");
+    for (Pat pat : {DENSE, SPARSE, SUM2}) dif_case(logn, logn + 3, 3, pat, false, "radix2-interpolation");
+  }
+}
+
+static void group_big() {
+  need_tables(24);
+  for (uint32_t logn : {22u, 23u})
+    for (int dit = 0; dit < 2; dit++) {
+      const size_t n = (size_t)1 << logn, total = 2 * n;
+      const uint64_t seed = ((uint64_t)logn << 32) ^ dit ^ 0x424947ull;
+      std::vector<felt> v(total), got(total);
+      fill_random(v, seed);
+      craft(v.data(), 2, logn, 0, dit != 0, DENSE, seed);
+      felt* d = DDST.get(total);
+      CK(hipMemcpy(d, v.data(), total * 16, hipMemcpyHostToDevice));
+      NttBatch nb{d, d, nullptr, n, n, 1, 1, 2};
+      launch_ntt(pf, st, nb, logn, dit != 0, dit ? TB.df : TB.di, logn + 1);
+      CK(hipStreamSynchronize(st));
+      CK(hipMemcpy(got.data(), d, total * 16, hipMemcpyDeviceToHost));
+      host_full(v.data(), 2, logn, dit != 0);
+      const size_t mism = count_mismatch(v.data(), got.data(), total);
+      unsigned long long cnt[5];
+      zkp_ntt_redo_waves_take(cnt);
+      const NttPlan pl = ntt_plan(logn, dit != 0, 2);
+      char name[160];
+      snprintf(name, sizeof name, "big n=2^%u %s dense batches=2 (passes %u+%u+%u)", logn, dit ? "DIT" : "DIF", pl.pass[0].K,
+               pl.pass[1].K, pl.n > 2 ? pl.pass[2].K : 0);
+      verdict(name, mism, cnt, 2u);
+    }
+}
+
+// the stage-wise host transform against host_ntt (host_stark.hpp) and the naive DFT
+static void self_check() {
+  need_tables(13);
+  for (int dit = 0; dit < 2; dit++) {
+    for (uint32_t logn : {11u, 12u}) {
+      std::vector<felt> v((size_t)1 << logn);
+      fill_random(v, 77 + logn + dit);
+      const std::vector<felt> want = logn == 11 ? naive(v, logn, dit != 0) : host_ref(v, logn, dit != 0);
+      std::vector<felt> w = v;
+      host_full(w.data(), 1, logn, dit != 0);
+      // and back through the inverse stages
+      std::vector<felt> back = w;
+      for (uint32_t s = logn; s-- > 0;) host_stage(back.data(), 1, logn, s, dit != 0, true);
+      if (count_mismatch(want.data(), w.data(), w.size()) || count_mismatch(back.data(), v.data(), v.size())) {
+        printf("host: the stage-wise transform disagrees with %s at 2^%u %s\n", logn == 11 ? "the naive DFT" : "host_ntt", logn,
+               dit ? "DIT" : "DIF");
+        bad++;
+      }
+    }
+  }
+}
+
+int main(int argc, char** argv) {
+  setvbuf(stdout, NULL, _IONBF, 0);
+  CK(hipStreamCreate(&st));
+  struct Group { const char* name; void (*run)(); };
+  const Group groups[] = {{"whole", group_whole},
+                          {"pass-dit", [] { group_pass(0); }},
+                          {"pass-dif", [] { group_pass(1); }},
+                          {"pass-9", [] { group_pass(2); }},
+                          {"lde", group_lde},
+                          {"forms", group_forms},
+                          {"radix2", group_radix2},
+                          {"big", group_big}};
+  for (int i = 1; i < argc; i++) {
+    bool known = false;
+    for (const Group& g : groups) known = known || !strcmp(argv[i], g.name);
+    if (!known) {
+      fprintf(stderr, "unknown group %s\n", argv[i]);
+      return 2;
+    }
+  }
+  unsigned long long cnt[5];
+  zkp_ntt_redo_waves_take(cnt);
+  self_check();
+  for (const Group& g : groups) {
+    bool sel = argc == 1;
+    for (int i = 1; i < argc; i++) sel = sel || !strcmp(argv[i], g.name);
+    if (!sel) continue;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int c0 = cases;
+    g.run();
+    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    printf("group %s: %d cases in %.2f s\n", g.name, cases - c0, sec);
+  }
+  printf("%s: %d cases, %d mismatching\n", COUNTING ? "ntt_check_count" : "ntt_check", cases, bad);
   return bad ? 1 : 0;
 }

@@ -164,6 +164,21 @@ __device__ __forceinline__ void bfly1(felt& x, felt& y, Rare& q) {
   y = d;
 }
 
+// ZKP_COUNT_REDO (tests/native/ntt_check.cpp builds this file with it, as eval_check does
+// kernels.hip): count the waves that take an exact recomputation, per site: slot 0 the
+// staged coset-scale reload, slot 1 + r register round r of the pass
+#ifdef ZKP_COUNT_REDO
+__device__ unsigned long long zkp_ntt_redo_waves[5];
+#define ZKP_NTT_REDO_TAKEN(site)                                                       \
+  do {                                                                                 \
+    if ((threadIdx.x & 63) == 0) atomicAdd(&zkp_ntt_redo_waves[site], 1ull);           \
+  } while (0)
+#else
+#define ZKP_NTT_REDO_TAKEN(site) \
+  do {                           \
+  } while (0)
+#endif
+
 // rounds of a K-stage pass: <= 3 stages each, larger first
 template <int K>
 struct NttRounds {
@@ -315,7 +330,10 @@ __device__ __forceinline__ void ntt8_tile(const Ntt8Args& a, uint32_t bidx, uint
     };
     Rare q;
     stage_in(std::true_type{}, q);
-    if (scale && q.any()) stage_in(std::false_type{}, q);
+    if (scale && q.any()) {
+      ZKP_NTT_REDO_TAKEN(0);
+      stage_in(std::false_type{}, q);
+    }
     __syncthreads();
   }
   uint32_t b0 = DIT ? 0 : K;
@@ -455,7 +473,10 @@ __device__ __forceinline__ void ntt8_tile(const Ntt8Args& a, uint32_t bidx, uint
     };
     Rare qq;
     round(std::true_type{}, qq);
-    if (qq.any()) round(std::false_type{}, qq);
+    if (qq.any()) {
+      ZKP_NTT_REDO_TAKEN(1 + r);
+      round(std::false_type{}, qq);
+    }
     if (!last || staged) __syncthreads();  // everyone has read this round's slots
 #pragma unroll
     for (int m = 0; m < 8; m++) {
@@ -500,6 +521,26 @@ void preload_ntt_module() {
   hipFuncAttributes fa;
   (void)hipFuncGetAttributes(&fa, (const void*)k_ntt_pass);
 }
+
+#ifdef ZKP_COUNT_REDO
+// host: the exact-pass waves of k_ntt8 per site since the last call (and reset)
+void zkp_ntt_redo_waves_take(unsigned long long out[5]) {
+  const unsigned long long z[5] = {0, 0, 0, 0, 0};
+  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(zkp_ntt_redo_waves), sizeof z);
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(zkp_ntt_redo_waves), z, sizeof z);
+}
+// host: stages of register round r of a K-stage pass (0 past its last round)
+int zkp_ntt_round_bits(int K, int r) {
+  switch (K) {
+#define ZKP_ROUND_BITS(KK) \
+  case KK:                 \
+    return r < NttRounds<KK>::n ? NttRounds<KK>::bits(r) : 0;
+    ZKP_ROUND_BITS(6) ZKP_ROUND_BITS(7) ZKP_ROUND_BITS(8) ZKP_ROUND_BITS(9) ZKP_ROUND_BITS(11)
+#undef ZKP_ROUND_BITS
+  }
+  return -1;
+}
+#endif
 
 static void launch_ntt_radix2(Prof& prof, hipStream_t s, const NttBatch& b, uint32_t logn, bool dit,
                               const felt* tw) {
