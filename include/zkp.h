@@ -335,7 +335,8 @@ void zkp_ctx_destroy(zkp_ctx* ctx);
 /* Free the idle stage-session context the ctx keeps for its next zkp_session_create
  * (at most one; it holds the last session's device buffers and domain tables). */
 int zkp_ctx_trim(zkp_ctx* ctx);
-/* Last error message for ctx (static storage owned by ctx). */
+/* The message of the context's last call that took ctx, empty after one that succeeded
+ * (storage owned by ctx, valid until its next call). */
 const char* zkp_last_error(const zkp_ctx* ctx);
 void zkp_free(void* p);
 

@@ -91,16 +91,18 @@ def opened_values(blob, groups):
     return out
 
 
-def run_session(ctx, name, ov, more_queries=(), before=None):
+def run_session(ctx, name, ov, more_queries=(), before=None, ref=None):
     """One session driven with the overrides `ov` (every other challenge is the one the
     oracle's coin drew under them): trace root, constraint evaluations, constraint root,
     OOD frame, every FRI layer root the channel callback sees, remainder, remainder
     commitment and the openings against the oracle. more_queries: further position sets
     asked of the same session, each against an oracle run with those positions.
     before: {stage name: callable(session)} run ahead of that stage (the refusals).
+    ref: reference(name, **ov) where the caller has computed it already (the oracle then
+    does not run inside this call).
     -> what the session returned, the oracle's stage values and proof sections."""
     _, trace, pub_el, opts, sp = shape_inputs(name)
-    st, sec = reference(name, **ov)
+    st, sec = ref if ref is not None else reference(name, **ov)
     com = sec["commitments"]
     L = layers(sp)
     before = before or {}

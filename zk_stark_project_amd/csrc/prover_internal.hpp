@@ -699,10 +699,13 @@ int prove_impl(zkp_ctx* ctx, zkp_comm* cm, int air_id, const felt* d_trace, uint
 void drain_streams(zkp_ctx* ctx);
 
 // an entry point's body: C++ failures become its ZKP_ERR_* status (never an
-// exception across the C ABI) with the message in ctx->err
+// exception across the C ABI) with the message in ctx->err. The text of an earlier
+// call is dropped first, so that a refusal without a message of its own reads
+// "status N" and not what another call left behind.
 template <typename F>
 int guarded(zkp_ctx* ctx, F&& f) {
   if (!ctx) return ZKP_ERR_ARGUMENT;
+  ctx->err.clear();
   try {
     int rc = f();
     if (rc && ctx->err.empty()) ctx->err = "status " + std::to_string(rc);
