@@ -379,6 +379,77 @@ int zkp_air_check_trace_device_pub(zkp_ctx* ctx, int air_id, const zkp_felt* pub
                                    const void* d_trace_cols, uint32_t width, uint64_t n, uint64_t* bad_row,
                                    uint32_t* bad_constraint, uint32_t* bad_assertion);
 
+/* Each transition constraint's actual degree on a trace in device memory: the other half of
+ * winterfell's debug-build checks (its evaluator compares every constraint's actual degree
+ * with the declared one). Registration only bounds a constraint's degree syntactically, with
+ * periodic values, constants and pub[i] counted as 0; but a periodic column of cycle c is a
+ * polynomial of degree n - n/c (winterfell: TransitionConstraintDegree::with_cycles), so a
+ * constraint can exceed what it declares, and terms that cancel or a pub value of zero can
+ * leave it below. The proof's shape (ce, composition columns C) comes from the declarations.
+ *
+ * degrees[i] receives the degree of constraint i as a polynomial, i.e. of the program applied
+ * to the trace columns' interpolants, the periodic columns' polynomials and the instance's pub
+ * (not divided by the transition divisor), or ZKP_DEGREE_ZERO for the zero polynomial. The
+ * trace need not satisfy the constraints and is only read. The report:
+ *   eval_blowup    E = max(2, next_pow2(B)), B the largest zkp_air_degree_bounds value. The
+ *                  degrees are measured on the n * E points g * <w_(n E)>: a constraint is a
+ *                  product of at most B polynomials of degree <= n - 1, so its degree is at most
+ *                  B (n - 1) < E n and nothing aliases. E does not depend on the declared
+ *                  degrees: an under-declared program is the case in which the proof's own n * ce
+ *                  points are too few.
+ *   columns        C of a proof of this id at this n (from the declared degrees)
+ *   columns_needed max(1, ceil((max_degree - (n - 1) + 1) / n)): the columns the largest
+ *                  quotient fills; 1 when every constraint is zero
+ *   first_under    the first i with degrees[i] > declared_i * (n - 1) (winterfell's comparison,
+ *                  per constraint); UINT32_MAX if none
+ *   proof_fits     the condition that decides whether a proof can verify. The transition divisor
+ *                  (x^n - 1) / (x - w^(n-1)) has degree n - 1, so the quotient of a constraint of
+ *                  degree D has D - (n - 1) + 1 coefficients; the C composition columns hold C n.
+ *                  D - n + 2 <= C n, i.e. max_degree <= (C + 1) n - 2 (or all zero): 1, else 0.
+ *                  When 0, the prover keeps C columns of the quotient and drops the rest, and the
+ *                  bytes zkp_prove returns verify nowhere; declaring the degree `minimal`
+ *                  = ceil(degree / (n - 1)) of the offending constraint repairs it.
+ * Status, all decided on the host before the first HIP call, in zkp_air_check_trace_device_pub's
+ * order (the context stays usable; zkp_last_error has a message): ZKP_ERR_ARGUMENT for a null
+ * ctx, d_trace_cols, degrees or report, and for n_pub set with null pub_elems;
+ * ZKP_ERR_UNSUPPORTED_AIR for a built-in or unregistered id; then whatever
+ * zkp_air_check_trace_device_pub returns for the same arguments (ZKP_ERR_TRACE_SHAPE,
+ * ZKP_ERR_PUB_INPUTS: the entry describes a proof of this shape, so "n divides d - 1" is refused
+ * here too); ZKP_ERR_ARGUMENT for capacity < num_constraints; ZKP_ERR_UNSUPPORTED_AIR for E > 32;
+ * ZKP_ERR_TRACE_SHAPE for n * E > 2^28. A HIP failure returns ZKP_ERR_DEVICE.
+ * Device work: the columns are interpolated and extended to the E cosets; k_program_columns runs
+ * the program once per point and chunk and stores the raw constraint values of K constraints at
+ * a time; each is interpolated by the composition's route (per-coset inverse NTT, cross-coset
+ * DFT keeping all E segments) and k_column_degrees finds its top non-zero coefficient. K is the
+ * largest count for which K * E * n felts stay within 2^22 (64 MiB), at least 1 and at most 128:
+ * beside the extended trace (width * E * n felts) the call holds two such chunk buffers, whatever
+ * num_constraints is. All of it lives in buffers of its own: no buffer, image or table of a proof
+ * or of the trace check is written. The call synchronises its stream once, to read the degrees.
+ * zkp_prove never calls it. */
+#define ZKP_DEGREE_ZERO UINT64_MAX /* the constraint is the zero polynomial on this trace */
+typedef struct zkp_air_degree_report {
+  uint32_t num_constraints;
+  uint32_t eval_blowup;
+  uint32_t columns;
+  uint32_t columns_needed;
+  uint64_t max_degree; /* largest actual degree, ZKP_DEGREE_ZERO if all are zero */
+  uint32_t first_under;
+  uint32_t proof_fits;
+} zkp_air_degree_report;
+int zkp_air_constraint_degrees_device(zkp_ctx* ctx, int air_id, const zkp_felt* pub_elems, uint64_t n_pub,
+                                      const void* d_trace_cols, uint32_t width, uint64_t n, uint64_t* degrees,
+                                      uint32_t capacity, zkp_air_degree_report* report);
+/* Host only, no context, thread-safe: per constraint, the syntactic degree with every periodic
+ * operand counted as 1 (ADD / SUB -> max, MUL -> sum, saturated at 255). ZKP_ERR_UNSUPPORTED_AIR
+ * for an id that is not registered, ZKP_ERR_ARGUMENT for a null pointer or capacity <
+ * num_constraints (*num_constraints is still set). */
+int zkp_air_degree_bounds(int air_id, uint8_t* bounds, uint32_t capacity, uint32_t* num_constraints);
+/* Host only, no context, thread-safe: the status zkp_air_constraint_degrees_device decides on the
+ * host for these arguments after its null-pointer checks (capacity apart), with the message in
+ * zkp_air_last_error; on ZKP_OK *eval_blowup = E and *chunk = K of such a call (both nullable). */
+int zkp_air_constraint_degrees_shape(int air_id, const zkp_felt* pub_elems, uint64_t n_pub, uint32_t width,
+                                     uint64_t n, uint32_t* eval_blowup, uint32_t* chunk);
+
 /* ---- multi-GPU: coset-sharded proving ----
  * One proof is split over `world` ranks by LDE coset (rank r owns the cosets
  * [r*B/world, (r+1)*B/world)); the exchange steps are leaf-digest all-to-alls

@@ -6,7 +6,7 @@ from .air import (MimcAir, MimcInputs, GlobalUpdateAir, GlobalUpdateInputs, Trai
                   TrainingUpdateInputs, AIR_MIMC, AIR_GLOBAL_UPDATE, AIR_TRAINING_UPDATE, AirProgram,
                   RegisteredAir)
 from .prover import TraceTable, Proof, Prover, MimcProver, GlobalUpdateProver, TrainingUpdateProver, verify
-from ._native import InvalidTrace, VerifierError
+from ._native import DegreeMismatch, DegreeReport, InvalidTrace, VerifierError
 from . import helper
 
 __all__ = ["P", "GENERATOR", "TWO_ADICITY", "ProofOptions", "FieldExtension", "BatchingMethod",
@@ -14,4 +14,4 @@ __all__ = ["P", "GENERATOR", "TWO_ADICITY", "ProofOptions", "FieldExtension", "B
            "AIR_GLOBAL_UPDATE", "AIR_TRAINING_UPDATE", "TraceTable", "Proof", "Prover",
            "MimcProver", "GlobalUpdateProver", "TrainingUpdateAir", "TrainingUpdateInputs",
            "TrainingUpdateProver", "helper", "verify", "VerifierError", "AirProgram", "RegisteredAir",
-           "InvalidTrace"]
+           "InvalidTrace", "DegreeMismatch", "DegreeReport"]

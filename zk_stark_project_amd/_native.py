@@ -44,8 +44,50 @@ class InvalidTrace(ValueError):
         self.row, self.constraint, self.assertion = row, constraint, assertion
 
 
+class DegreeReport:
+    """What Context.constraint_degrees* returns (zkp_air_constraint_degrees_device): per transition
+    constraint, the degree of the polynomial it is on the trace. `actual[i]` is None for the zero
+    polynomial; `declared` the registered degrees; `minimal[i]` = max(1, ceil(actual / (n - 1))),
+    the smallest degree that could be declared (1 for zero); `under` the constraints above
+    declared * (n - 1), `over` those whose minimal degree is below the declared one;
+    `columns` the composition columns of a proof (from the declared degrees), `columns_needed`
+    those the largest quotient fills, and `proof_fits` whether a proof of this shape can verify."""
+
+    def __init__(self, n, actual, declared, eval_blowup, columns, columns_needed, max_degree, first_under, proof_fits):
+        self.n, self.actual, self.declared = n, actual, declared
+        self.minimal = [1 if a is None else max(1, -(-a // (n - 1))) for a in actual]
+        self.under = [i for i, a in enumerate(actual) if a is not None and a > declared[i] * (n - 1)]
+        self.over = [i for i, m in enumerate(self.minimal) if m < declared[i]]
+        self.eval_blowup, self.columns, self.columns_needed = eval_blowup, columns, columns_needed
+        self.max_degree, self.first_under, self.proof_fits = max_degree, first_under, proof_fits
+
+    def __repr__(self):
+        return (f"DegreeReport(actual={self.actual}, declared={self.declared}, minimal={self.minimal}, "
+                f"columns={self.columns}, columns_needed={self.columns_needed}, proof_fits={self.proof_fits})")
+
+
+class DegreeMismatch(ValueError):
+    """Context.prove / prove_device with check_degrees=True: a constraint's actual degree does not
+    fit the composition columns its declared degree provides, so no proof would verify. `.report`
+    is the DegreeReport; declaring report.minimal[i] for the constraints in report.under repairs it."""
+
+    def __init__(self, report):
+        super().__init__(f"constraints {report.under} exceed their declared degrees: the proof has "
+                         f"{report.columns} composition columns and needs {report.columns_needed} "
+                         f"(actual {report.actual}, declared {report.declared}, minimal {report.minimal})")
+        self.report = report
+
+
 class Felt(ctypes.Structure):
     _fields_ = [("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64)]
+
+
+class AirDegreeReportC(ctypes.Structure):
+    """`zkp_air_degree_report` (include/zkp.h)."""
+    _fields_ = [("num_constraints", ctypes.c_uint32), ("eval_blowup", ctypes.c_uint32),
+                ("columns", ctypes.c_uint32), ("columns_needed", ctypes.c_uint32),
+                ("max_degree", ctypes.c_uint64), ("first_under", ctypes.c_uint32),
+                ("proof_fits", ctypes.c_uint32)]
 
 
 class Transcript(ctypes.Structure):
@@ -95,6 +137,7 @@ EXPORTED = [
     "zkp_air_register", "zkp_air_unregister", "zkp_air_last_error", "zkp_air_check_trace",
     "zkp_air_check_trace_device", "zkp_air_register_strided",
     "zkp_air_register_params", "zkp_air_check_trace_pub", "zkp_air_check_trace_device_pub",
+    "zkp_air_constraint_degrees_device", "zkp_air_degree_bounds", "zkp_air_constraint_degrees_shape",
 ]
 
 # zkp_host_transport callbacks (include/zkp.h)
@@ -300,6 +343,11 @@ def load():
                                               ctypes.POINTER(u32)]
         L.zkp_air_check_trace_device_pub.argtypes = [vp, i32, vp, u64, vp, u32, u64, ctypes.POINTER(u64),
                                                      ctypes.POINTER(u32), ctypes.POINTER(u32)]
+        L.zkp_air_constraint_degrees_device.argtypes = [vp, i32, vp, u64, vp, u32, u64, vp, u32,
+                                                        ctypes.POINTER(AirDegreeReportC)]
+        L.zkp_air_degree_bounds.argtypes = [i32, vp, u32, ctypes.POINTER(u32)]
+        L.zkp_air_constraint_degrees_shape.argtypes = [i32, vp, u64, u32, u64, ctypes.POINTER(u32),
+                                                       ctypes.POINTER(u32)]
         _lib = L
         return L
 
@@ -382,6 +430,34 @@ def air_check_trace(air, trace: np.ndarray, pub=None):
         return None
     none = 2**32 - 1
     return (row.value, None if con.value == none else con.value, None if asr.value == none else asr.value)
+
+
+def air_degree_bounds(air) -> list:
+    """zkp_air_degree_bounds: per constraint, the syntactic degree with every periodic operand
+    counted as 1 (host only)."""
+    L = load()
+    cnt = ctypes.c_uint32()
+    buf = (ctypes.c_uint8 * 1024)()  # ZKP_AIR_MAX_CONSTRAINTS
+    rc = L.zkp_air_degree_bounds(_air(air), buf, 1024, ctypes.byref(cnt))
+    if rc:
+        raise ZkpError(rc, "zkp_air_degree_bounds: " + (L.zkp_air_last_error() or b"").decode(errors="replace"))
+    return list(buf[:cnt.value])
+
+
+def air_constraint_degrees_shape(air, width: int, n: int, pub=None):
+    """zkp_air_constraint_degrees_shape (host only): (eval_blowup E, chunk K) of a
+    Context.constraint_degrees_device call with these arguments; raises ZkpError with the status
+    that call would return."""
+    L = load()
+    e, k = ctypes.c_uint32(), ctypes.c_uint32()
+    pub = list(pub) if pub is not None else []
+    pubb = b"".join(int(v).to_bytes(16, "little") for v in pub)
+    rc = L.zkp_air_constraint_degrees_shape(_air(air), pubb if pub else None, len(pub), int(width), int(n),
+                                            ctypes.byref(e), ctypes.byref(k))
+    if rc:
+        raise ZkpError(rc, "zkp_air_constraint_degrees_shape: " +
+                       (L.zkp_air_last_error() or b"").decode(errors="replace"))
+    return e.value, k.value
 
 
 def mimc_trace(seed: int, n: int) -> np.ndarray:
@@ -562,12 +638,53 @@ class Context:
         finally:
             self.free(d)
 
-    def prove(self, air_id: int, trace: np.ndarray, pub, options: ProofOptions, device_ptr=None, validate=False):
+    def constraint_degrees_device(self, air, d_trace: int, width: int, n: int, pub=None) -> DegreeReport:
+        """zkp_air_constraint_degrees_device on a (width, n) column-major trace in device memory:
+        the DegreeReport of every transition constraint's actual degree on that trace. `pub`: the
+        instance's public inputs, for an id registered with them. `air` is a RegisteredAir (its
+        declared degrees are what the actual ones are compared with). Synchronises the context's stream."""
+        pub = list(pub) if pub is not None else []
+        pubb = b"".join(int(v).to_bytes(16, "little") for v in pub)
+        cap = 1024  # ZKP_AIR_MAX_CONSTRAINTS
+        deg = (ctypes.c_uint64 * cap)()
+        rep = AirDegreeReportC()
+        rc = self.lib.zkp_air_constraint_degrees_device(self.ptr, _air(air), pubb if pub else None, len(pub),
+                                                        d_trace, int(width), int(n), deg, cap, ctypes.byref(rep))
+        self._check(rc, "zkp_air_constraint_degrees_device")
+        zero = 2**64 - 1
+        actual = [None if deg[i] == zero else int(deg[i]) for i in range(rep.num_constraints)]
+        declared = list(getattr(air, "degrees", None) or [])
+        if len(declared) != len(actual):
+            raise ValueError("constraint_degrees_device takes a RegisteredAir (its declared degrees are compared)")
+        return DegreeReport(int(n), actual, declared, rep.eval_blowup, rep.columns, rep.columns_needed,
+                            None if rep.max_degree == zero else int(rep.max_degree),
+                            None if rep.first_under == 2**32 - 1 else int(rep.first_under), bool(rep.proof_fits))
+
+    def constraint_degrees(self, air, trace: np.ndarray, pub=None) -> DegreeReport:
+        """constraint_degrees_device on a host (width, n, 2) uint64 array: alloc, upload, measure, free."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        d = self.alloc(trace.nbytes)
+        try:
+            self.to_device(d, trace)
+            return self.constraint_degrees_device(air, d, int(trace.shape[0]), int(trace.shape[1]), pub)
+        finally:
+            self.free(d)
+
+    def prove(self, air_id: int, trace: np.ndarray, pub, options: ProofOptions, device_ptr=None, validate=False,
+              check_degrees=False):
         """trace: (width, n, 2) uint64 host array (ignored when device_ptr is given).
         validate=True (registered ids; a built-in id raises ZkpError UNSUPPORTED_AIR) checks the
-        trace on the device first and raises InvalidTrace before any proving work."""
+        trace on the device first and raises InvalidTrace before any proving work.
+        check_degrees=True (a RegisteredAir) measures every constraint's actual degree on the device
+        first and raises DegreeMismatch, before any proving work, when the proof's composition
+        columns cannot hold it (DegreeReport.proof_fits)."""
         w, n = int(trace.shape[0]), int(trace.shape[1])
         vpub = list(pub) if getattr(air_id, "num_pub", 0) else None  # an id with public inputs checks its instance
+        if check_degrees:
+            rep = (self.constraint_degrees(air_id, trace, vpub) if device_ptr is None
+                   else self.constraint_degrees_device(air_id, device_ptr, w, n, vpub))
+            if not rep.proof_fits:
+                raise DegreeMismatch(rep)
         air_id = _air(air_id)
         if validate:
             bad = (self.check_trace_pub(air_id, vpub, trace) if device_ptr is None
@@ -631,9 +748,10 @@ class Context:
                     "zkp_comm_rccl_create")
         return Comm(p.value)
 
-    def prove_device(self, air_id, d_trace, width, n, pub, options, validate=False):
+    def prove_device(self, air_id, d_trace, width, n, pub, options, validate=False, check_degrees=False):
         shape = np.empty((width, n, 0))
-        return self.prove(air_id, shape, pub, options, device_ptr=d_trace, validate=validate)
+        return self.prove(air_id, shape, pub, options, device_ptr=d_trace, validate=validate,
+                          check_degrees=check_degrees)
 
     # -- device memory ------------------------------------------------------
     def alloc(self, nbytes: int) -> int:

@@ -259,6 +259,7 @@ class RegisteredAir:
         self.AIR_ID = air_id
         self.WIDTH = program.width
         self.num_constraints = len(program.constraints)
+        self.degrees = [d for _, d in program.constraints]  # the declared degrees
         self.num_assertions = len(program.assertions) + len(program.strided_assertions)
         self.num_coeffs = self.num_constraints + self.num_assertions  # composition coefficients
         self.num_pub = program.num_pub  # 0: concrete values; else every proof's pub has this length
@@ -279,6 +280,16 @@ class RegisteredAir:
     def check_trace_device_pub(self, ctx, pub, d_trace, n):
         """The same for an id with public inputs, against the instance `pub` states."""
         return ctx.check_trace_device_pub(self.AIR_ID, pub, d_trace, self.WIDTH, n)
+
+    def constraint_degrees_device(self, ctx, d_trace, n, pub=None):
+        """Context.constraint_degrees_device for this id: the DegreeReport of the trace
+        (WIDTH x n, in device memory); `pub` for an id with public inputs."""
+        return ctx.constraint_degrees_device(self, d_trace, self.WIDTH, n, pub)
+
+    def degree_bounds(self):
+        """zkp_air_degree_bounds: per constraint, the syntactic degree with periodic operands counted as 1."""
+        from . import _native
+        return _native.air_degree_bounds(self.AIR_ID)
 
     def close(self):
         if self.AIR_ID is not None:
@@ -583,3 +594,15 @@ class AirProgram:
         """The same check on the device (Context.check_trace on a host trace)."""
         with self.register() as air:
             return ctx.check_trace_pub(air, pub, trace)
+
+    def constraint_degrees(self, ctx, trace, pub=None):
+        """Context.constraint_degrees on a host (width, n, 2) uint64 trace: every constraint's
+        actual degree on that trace, as a DegreeReport (registers and frees an id)."""
+        with self.register() as air:
+            return ctx.constraint_degrees(air, trace, pub)
+
+    def degree_bounds(self):
+        """zkp_air_degree_bounds of this program: per constraint, the syntactic degree with every
+        periodic operand counted as 1 (host only; registers and frees an id)."""
+        with self.register() as air:
+            return air.degree_bounds()

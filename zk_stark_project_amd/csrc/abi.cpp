@@ -575,6 +575,124 @@ int zkp_air_check_trace_device_pub(zkp_ctx* ctx, int air_id, const zkp_felt* pub
   });
 }
 
+// Each transition constraint's actual degree on a trace in device memory (include/zkp.h).
+// Every refusal is degrees_plan's (host_stark.hpp) or the capacity check, before the first
+// HIP call. Every buffer is this entry's own ("deg_*"); the domain tables it shares with
+// proofs (twiddles, S, Si) depend on the shape alone and are only ever filled with the same values.
+int zkp_air_constraint_degrees_device(zkp_ctx* ctx, int air_id, const zkp_felt* pub_elems, uint64_t n_pub,
+                                      const void* d_trace_cols, uint32_t width, uint64_t n, uint64_t* degrees,
+                                      uint32_t capacity, zkp_air_degree_report* report) {
+  return guarded(ctx, [&] {  // a null ctx returns ZKP_ERR_ARGUMENT there
+    if (!d_trace_cols || !degrees || !report || (n_pub && !pub_elems)) {
+      ctx->err = "d_trace_cols, degrees, report or (with n_pub set) pub_elems: null";
+      return (int)ZKP_ERR_ARGUMENT;
+    }
+    DegreesPlan pl;
+    const int rc = degrees_plan(air_id, pub_elems, n_pub, width, n, pl, ctx->err);
+    if (rc) return rc;
+    const airp::Program& pr = *pl.air.prog;
+    if (capacity < pr.num_t) {
+      ctx->err = "capacity: below num_constraints (" + std::to_string(pr.num_t) + ")";
+      return (int)ZKP_ERR_ARGUMENT;
+    }
+    HIP_CHECK(hipSetDevice(ctx->device));
+    const uint32_t E = pl.E, logE = ilog2(E), logn = ilog2(n), logN = logn + logE;
+    const uint64_t M = n * E;
+    ctx->ensure_coset(logn, logE, logE);
+    // the image: the code sections with each periodic column over the E*n domain (as the
+    // evaluation image's at scale ce); a context keeps the last (id, n, E)'s
+    const ProgCodeLayout lay(pr, E);
+    const size_t total = lay.end();
+    felt* dimg = ctx->buf<felt>("deg_image", total);
+    std::vector<felt>& tag = ctx->host_cache["deg_image_tag"];
+    const felt want[2] = {make((uint64_t)air_id, logn), make(logE, total)};
+    if (tag.size() != 2 || !eq(tag[0], want[0]) || !eq(tag[1], want[1])) {
+      tag.clear();
+      std::vector<felt> img(total, zero());
+      lay.write(img.data());
+      const felt g = felt_u64(3);
+      for (size_t p = 0; p < pr.periodic.size(); p++) {
+        const size_t cyc = pr.periodic[p].size();
+        std::vector<felt> kc = pr.periodic[p];
+        host_interpolate(kc, one());
+        const std::vector<felt> kv = host_evaluate(kc, cyc * E, pow_u64(g, n / cyc));
+        memcpy(img.data() + lay.tab[p], kv.data(), kv.size() * 16);
+      }
+      ctx->upload(dimg, img.data(), total * 16);
+      if (total * 16 > (1u << 20)) ctx->sync();  // past the ring's size the copy reads `img` itself
+      tag.assign(want, want + 2);
+    }
+    ProgCode code = lay.code(dimg);
+    if (pr.num_pub) {  // the instance's pub table (pr.pub lives until the download below has synchronised)
+      felt* dpub = ctx->buf<felt>("deg_pub", pr.num_pub);
+      ctx->upload(dpub, pr.pub.data(), (size_t)pr.num_pub * 16);
+      code.pub = dpub;
+    }
+    // 1. the columns' coefficients, then their values on the E cosets g w_N^j <w_n> (the trace LDE's route)
+    felt* coef = ctx->buf<felt>("deg_coef", (size_t)width * n);
+    felt* ext = ctx->buf<felt>("deg_ext", (size_t)width * M);
+    NttBatch ib{(const felt*)d_trace_cols, coef, nullptr, n, n, 1, 1, width};
+    launch_ntt(ctx->prof, ctx->stream, ib, logn, false, ctx->itws(logN), logN);
+    NttBatch lb{coef, ext, ctx->S(logn, logE), n, n, E, E, width * E};
+    launch_ntt(ctx->prof, ctx->stream, lb, logn, true, ctx->tws(logN), logN);
+    // the cross-coset DFT's constants, all E segments kept (shape-only)
+    const std::string dkey = "deg_dft_" + std::to_string(logn) + "_" + std::to_string(logE);
+    felt* dcoefs = ctx->buf<felt>(dkey + "_coefs", (size_t)E + E / 2);
+    uint32_t* dblk = ctx->buf<uint32_t>(dkey + "_blk", E);
+    if (!ctx->have_cached(dkey)) {
+      const std::vector<felt> dc = comp_dft_consts(n, logE, E);
+      std::vector<uint32_t> blk(E);
+      for (uint32_t u = 0; u < E; u++) blk[u] = u;
+      ctx->upload(dcoefs, dc.data(), dc.size() * 16);
+      ctx->upload(dblk, blk.data(), blk.size() * 4);
+    }
+    const uint32_t K = std::min(pl.K, pr.num_t);
+    felt* vals = ctx->buf<felt>("deg_vals", (size_t)K * M);
+    felt* cf = ctx->buf<felt>("deg_coefs", (size_t)K * M);
+    long long* ddeg = ctx->buf<long long>("deg_result", pr.num_t);
+    HIP_CHECK(hipMemsetAsync(ddeg, 0xff, (size_t)pr.num_t * 8, ctx->stream));
+    for (uint32_t i0 = 0; i0 < pr.num_t; i0 += K) {
+      const uint32_t k = std::min(K, pr.num_t - i0);
+      // 2. the chunk's raw constraint values; 3. each one's coefficients by the composition's
+      // route: per-coset inverse NTTs (in place), then the E-point DFT with its twists per column
+      launch_program_columns(ctx->prof, ctx->stream, code, ext, width, logn, logE, i0, k, vals);
+      NttBatch cb{vals, vals, nullptr, n, n, 1, 1, k * E};
+      launch_ntt(ctx->prof, ctx->stream, cb, logn, false, ctx->itws(logN), logN);
+      for (uint32_t c = 0; c < k; c++)
+        launch_comp_dft(ctx->prof, ctx->stream, vals + (size_t)c * M, dblk, ctx->Si(logn, logE, logE), dcoefs, E, E,
+                        logn, 0, n, cf + (size_t)c * M);
+      // 4. the top non-zero coefficient of each
+      launch_column_degrees(ctx->prof, ctx->stream, cf, logn, logE, k, ddeg + i0);
+    }
+    std::vector<uint64_t> h(pr.num_t);
+    ctx->download(h.data(), ddeg, (size_t)pr.num_t * 8);  // the call's one stream synchronise
+    ctx->collect_prof();
+    ctx->free_retired();
+    zkp_air_degree_report r{};
+    r.num_constraints = pr.num_t;
+    r.eval_blowup = E;
+    r.columns = pl.air.comp_cols();
+    r.max_degree = ZKP_DEGREE_ZERO;
+    r.first_under = UINT32_MAX;
+    for (uint32_t i = 0; i < pr.num_t; i++) {
+      degrees[i] = h[i];
+      if (h[i] == ZKP_DEGREE_ZERO) continue;
+      if (r.max_degree == ZKP_DEGREE_ZERO || h[i] > r.max_degree) r.max_degree = h[i];
+      if (r.first_under == UINT32_MAX && h[i] > (uint64_t)pr.degrees[i] * (n - 1)) r.first_under = i;
+    }
+    r.columns_needed = 1;
+    r.proof_fits = 1;
+    if (r.max_degree != ZKP_DEGREE_ZERO) {
+      // the quotient by the transition divisor (degree n - 1) has max_degree - (n - 1) + 1 coefficients
+      if (r.max_degree + 2 > n) r.columns_needed = (uint32_t)((r.max_degree + 2 - n + n - 1) / n);
+      if (r.columns_needed < 1) r.columns_needed = 1;
+      r.proof_fits = r.max_degree <= ((uint64_t)r.columns + 1) * n - 2;
+    }
+    *report = r;
+    return 0;
+  });
+}
+
 // Host-side MiMC AIR trace builder (trace construction, like TraceTable building
 // in the reference; not part of the proving hot path).
 int zkp_build_mimc_trace(const uint8_t seed[16], uint64_t n, zkp_felt* out) {

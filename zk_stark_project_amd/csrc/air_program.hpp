@@ -339,6 +339,35 @@ inline void evaluate(const Program& pr, const felt* cur, const felt* nxt, const 
   }
 }
 
+// Each constraint's syntactic degree with every periodic operand counted as 1 (validate()
+// counts it as 0): ADD / SUB -> max, MUL -> sum, saturated at 255. A product of that many
+// trace and periodic columns over n rows has degree at most bound * (n - 1), so the bound
+// sizes the domain on which a constraint's actual degree can be measured without aliasing
+// (zkp_air_constraint_degrees_device). `pr` has passed validate().
+inline std::vector<uint8_t> degree_bounds(const Program& pr) {
+  uint32_t rdeg[ZKP_AIR_MAX_REGISTERS] = {};
+  auto deg = [&](uint32_t o) -> uint32_t {
+    switch (src_kind(o)) {
+      case ZKP_SRC_REG: return rdeg[src_index(o)];
+      case ZKP_SRC_CUR:
+      case ZKP_SRC_NEXT:
+      case ZKP_SRC_PERIODIC: return 1;
+      default: return 0;
+    }
+  };
+  std::vector<uint8_t> out;
+  for (uint64_t op : pr.ops) {
+    const uint32_t da = deg(op_a(op));
+    if (op_code(op) == ZKP_OP_EMIT) {
+      out.push_back((uint8_t)da);
+      continue;
+    }
+    const uint32_t db = deg(op_b(op));
+    rdeg[op_dst(op)] = std::min(255u, op_code(op) == ZKP_OP_MUL ? da + db : std::max(da, db));
+  }
+  return out;
+}
+
 // ---- the process-wide table (ids from ZKP_AIR_FIRST_ID, never reused)
 struct Registry {
   std::mutex mu;

@@ -284,6 +284,55 @@ inline int build_air(AirDesc& a, int id, uint32_t w, uint64_t n, const std::vect
   return ZKP_ERR_UNSUPPORTED_AIR;
 }
 
+// What zkp_air_constraint_degrees_device decides on the host, after its null-pointer checks and
+// before the capacity one, in zkp_air_check_trace_device_pub's order: the instance, the domain
+// factor E = max(2, next_pow2(largest degree bound)) and the chunk K. `err` receives a message.
+struct DegreesPlan {
+  AirDesc air;
+  uint32_t E = 0, K = 0;
+};
+inline int degrees_plan(int air_id, const zkp_felt* pub_elems, uint64_t n_pub, uint32_t width, uint64_t n,
+                        DegreesPlan& pl, std::string& err) {
+  if (air_id == ZKP_AIR_MIMC || air_id == ZKP_AIR_GLOBAL_UPDATE || air_id == ZKP_AIR_TRAINING_UPDATE) {
+    err = "air_id: a built-in id has no constraint program";
+    return ZKP_ERR_UNSUPPORTED_AIR;
+  }
+  if (n < 8 || (n & (n - 1)) || width == 0 || width > 255) {
+    err = "n must be a power of two >= 8 and width 1..255";
+    return ZKP_ERR_TRACE_SHAPE;
+  }
+  std::vector<felt> pub(n_pub);
+  for (uint64_t i = 0; i < n_pub; i++) pub[i] = make(pub_elems[i].lo, pub_elems[i].hi);
+  const int rc = build_air(pl.air, air_id, width, n, pub);
+  if (rc) {
+    err = rc == ZKP_ERR_UNSUPPORTED_AIR ? "air_id: not a registered id"
+                                        : "the id has no proof of this width, n and pub_elems";
+    return rc;
+  }
+  if (!pl.air.prog->num_pub && n_pub) {
+    err = "n_pub: the id takes no public inputs";
+    return ZKP_ERR_PUB_INPUTS;
+  }
+  if (n > (1ull << MAX_LOG_TRACE)) {
+    err = "n: above 2^23, the longest trace the prover takes";
+    return ZKP_ERR_TRACE_SHAPE;
+  }
+  uint32_t B = 0;
+  for (uint8_t b : airp::degree_bounds(*pl.air.prog)) B = std::max<uint32_t>(B, b);
+  pl.E = 2;
+  while (pl.E < B) pl.E <<= 1;
+  if (pl.E > 32) {
+    err = "a constraint's degree bound is " + std::to_string(B) + ": domain factors above 32 are not supported";
+    return ZKP_ERR_UNSUPPORTED_AIR;
+  }
+  if (n * pl.E > (1ull << MAX_LOG_DOMAIN)) {
+    err = "n * eval_blowup exceeds 2^28";
+    return ZKP_ERR_TRACE_SHAPE;
+  }
+  pl.K = degrees_chunk(n, pl.E);
+  return 0;
+}
+
 inline int check_options(const zkp_proof_options* o) {
   if (!o) return ZKP_ERR_ARGUMENT;
   if (o->field_extension != ZKP_FIELD_EXTENSION_NONE) return ZKP_ERR_UNSUPPORTED_FIELD_EXTENSION;

@@ -660,6 +660,45 @@ __global__ __launch_bounds__(PROG_TPB) void k_check_program(ProgCheckArgs a, con
     atomicMin(res, (unsigned long long)((r << 10) | bad));
 }
 
+// The raw values of a program's constraints over E cosets of the trace (launch_program_columns):
+// point q = j*n + t (coset j, row t) per thread, x = g w_(nE)^j w_n^t. CUR column c is
+// ext[c*E*n + q], NEXT the same coset's row t + 1 (x w_n; the last row wraps to the coset's
+// first: the polynomials are evaluated, not the trace's rows), PERIODIC the column over the
+// E*n domain at the natural index j + E*t. EMIT i is wave-uniform: inside the chunk its
+// operand is stored, coalesced over q; nothing else is written.
+__global__ __launch_bounds__(PROG_TPB) void k_program_columns(ProgCode code, const felt* __restrict__ ext,
+                                                              uint32_t logn, uint32_t logE, uint32_t i0, uint32_t K,
+                                                              felt* __restrict__ out) {
+  lds_u32x4* const rg = prog_regs();
+  const uint64_t M = 1ull << (logn + logE), nmask = (1ull << logn) - 1;
+  const uint64_t q = (uint64_t)blockIdx.x * PROG_TPB + threadIdx.x;
+  if (q >= M) return;
+  const uint64_t t = q & nmask;
+  run_program<false>(code, rg, ext + q, ext + (q - t) + ((t + 1) & nmask), M, (uint32_t)((q >> logn) + (t << logE)),
+                     nullptr, [&](uint32_t i, felt v) {
+                       if (i - i0 < K) out[(uint64_t)(i - i0) * M + q] = v;
+                     });
+}
+
+// The highest non-zero coefficient of each column (launch_column_degrees): element e = m*n + p
+// of column k = blockIdx.y holds coefficient m*n + rev(p). A lane's key is that index + 1, or 0
+// for a zero element; the wave's maximum by a butterfly of shuffles, then lane 0 of a wave that
+// saw a non-zero value does one signed 64-bit atomicMax on deg[k], which the host preset to -1:
+// a zero column issues no atomic and keeps it.
+__global__ __launch_bounds__(TPB) void k_column_degrees(const felt* __restrict__ coefs, uint32_t logn, uint32_t logE,
+                                                        long long* __restrict__ deg) {
+  const uint64_t M = 1ull << (logn + logE);
+  const uint64_t e = (uint64_t)blockIdx.x * TPB + threadIdx.x;
+  uint32_t key = 0;  // M <= 2^MAX_LOG_DOMAIN: an index + 1 fits
+  if (e < M) {
+    const felt v = coefs[blockIdx.y * M + e];
+    const uint32_t p = (uint32_t)e & ((1u << logn) - 1);
+    if (!is_zero(v)) key = ((uint32_t)e - p + rev_bits(p, logn)) + 1;
+  }
+  for (int off = 32; off; off >>= 1) key = max(key, (uint32_t)__shfl_xor((int)key, off));
+  if (key && (threadIdx.x & 63) == 0) atomicMax(deg + blockIdx.y, (long long)key - 1);
+}
+
 // Linear AIRs. TRANS: transition sum_c a_c*next_c + b_c*cur_c divided by Z_T
 // (GlobalUpdate); without it the transition part is identically zero
 // (TrainingUpdate). Boundary: group 0 = sum_c beta0_c*cur_c - bconst0
@@ -1660,6 +1699,25 @@ void launch_check_program(Prof& prof, hipStream_t s, ProgCheckArgs a, uint32_t w
          hipLaunchKernelGGL(k_check_program, dim3(blocks), dim3(PROG_TPB), lds, s, a, T, res));
 }
 
+void launch_program_columns(Prof& prof, hipStream_t s, const ProgCode& code, const felt* ext, uint32_t width,
+                            uint32_t logn, uint32_t logE, uint32_t i0, uint32_t K, felt* out) {
+  const size_t lds = prog_lds_bytes(code, "constraint degrees outside the kernel's limits");
+  if (logn + logE > MAX_LOG_DOMAIN || !K) launch_fail(ZKP_ERR_ARGUMENT, "constraint degrees outside the kernel's limits");
+  const uint64_t M = 1ull << (logn + logE);
+  LAUNCH(prof, "program_columns", s, (double)M * (width + K) * 16.0,
+         hipLaunchKernelGGL(k_program_columns, dim3(blocks_for(M, PROG_TPB)), dim3(PROG_TPB), lds, s, code, ext, logn,
+                            logE, i0, K, out));
+}
+
+void launch_column_degrees(Prof& prof, hipStream_t s, const felt* coefs, uint32_t logn, uint32_t logE, uint32_t K,
+                           long long* deg) {
+  if (logn + logE > MAX_LOG_DOMAIN || !K || K > DEG_CHUNK_MAX)
+    launch_fail(ZKP_ERR_ARGUMENT, "constraint degrees outside the kernel's limits");
+  const uint64_t M = 1ull << (logn + logE);
+  LAUNCH(prof, "column_degrees", s, (double)M * K * 16.0,
+         hipLaunchKernelGGL(k_column_degrees, dim3(blocks_for(M), K), dim3(TPB), 0, s, coefs, logn, logE, deg));
+}
+
 void launch_eval_linear(Prof& prof, hipStream_t s, const EvalCommon& c, const LinearEvalArgs& a, const felt* lde,
                         felt* comp) {
   uint64_t M = (uint64_t)c.cel << c.logn;
@@ -1810,7 +1868,10 @@ void launch_comp_dft(Prof& prof, hipStream_t s, const felt* recv, const uint32_t
                                                                    consts, C, logn, p0, nR, out, hi_flag)); break;
     case 16: LAUNCH(prof, "comp_dft", s, bytes, hipLaunchKernelGGL(k_comp_dft<16>, g, dim3(TPB), 0, s, recv, blk,
                                                                     Si, consts, C, logn, p0, nR, out, hi_flag)); break;
-    default: launch_fail(ZKP_ERR_UNSUPPORTED_AIR, "composition DFT supports ce in {2, 4, 8, 16}");
+    // 32 cosets: zkp_air_constraint_degrees_device alone (a proof's ce is at most 16)
+    case 32: LAUNCH(prof, "comp_dft", s, bytes, hipLaunchKernelGGL(k_comp_dft<32>, g, dim3(TPB), 0, s, recv, blk,
+                                                                    Si, consts, C, logn, p0, nR, out, hi_flag)); break;
+    default: launch_fail(ZKP_ERR_UNSUPPORTED_AIR, "composition DFT supports ce in {2, 4, 8, 16, 32}");
   }
 }
 

@@ -517,6 +517,46 @@ extern "C" int zkp_air_unregister(int air_id) {
 
 extern "C" const char* zkp_air_last_error(void) { return airp::last_error().c_str(); }
 
+extern "C" int zkp_air_degree_bounds(int air_id, uint8_t* bounds, uint32_t capacity, uint32_t* num_constraints) {
+  std::string& err = airp::last_error();
+  err.clear();
+  if (!bounds || !num_constraints) return ZKP_ERR_ARGUMENT;
+  try {
+    const auto pr = airp::lookup(air_id);
+    if (!pr) {
+      err = "air_id: not a registered id";
+      return ZKP_ERR_UNSUPPORTED_AIR;
+    }
+    *num_constraints = pr->num_t;
+    if (capacity < pr->num_t) {
+      err = "capacity: below num_constraints";
+      return ZKP_ERR_ARGUMENT;
+    }
+    const std::vector<uint8_t> b = airp::degree_bounds(*pr);
+    memcpy(bounds, b.data(), b.size());
+    return ZKP_OK;
+  } catch (const std::bad_alloc&) {
+    return ZKP_ERR_OOM;
+  }
+}
+
+extern "C" int zkp_air_constraint_degrees_shape(int air_id, const zkp_felt* pub_elems, uint64_t n_pub, uint32_t width,
+                                                uint64_t n, uint32_t* eval_blowup, uint32_t* chunk) {
+  std::string& err = airp::last_error();
+  err.clear();
+  if (n_pub && !pub_elems) return ZKP_ERR_ARGUMENT;
+  try {
+    DegreesPlan pl;
+    const int rc = degrees_plan(air_id, pub_elems, n_pub, width, n, pl, err);
+    if (rc) return rc;
+    if (eval_blowup) *eval_blowup = pl.E;
+    if (chunk) *chunk = pl.K;
+    return ZKP_OK;
+  } catch (const std::bad_alloc&) {
+    return ZKP_ERR_OOM;
+  }
+}
+
 // Host trace validation for a registered constraint program (include/zkp.h): the
 // interpreter of air_program.hpp on every frame (rows r, r+1; periodic column p at
 // row r is its value r mod cycle), then the assertions in their stored order.

@@ -412,6 +412,26 @@ struct ProgCheckArgs {
 void launch_check_program(Prof& prof, hipStream_t s, ProgCheckArgs a, uint32_t width, const felt* T,
                           unsigned long long* res, uint64_t strided_blocks = 0);
 
+// The raw constraint values of a registered program over E = 2^logE cosets of the trace
+// (k_program_columns; zkp_air_constraint_degrees_device): ext holds the columns extended
+// coset-major (column c, coset j, row t at (c*E + j)*n + t), one point q = j*n + t per thread.
+// EMIT i of the chunk [i0, i0 + K) stores its operand at out[(i - i0)*E*n + q]; no
+// coefficients, divisor or assertions. code: periodic tables over the E*n domain, indexed by
+// the natural index j + E*t (mask = cycle*E - 1), as ProgEvalArgs' over the CE domain.
+constexpr uint64_t DEG_CHUNK_FELTS = 1ull << 22;  // K*E*n felts of a chunk stay within this (64 MiB) ...
+constexpr uint32_t DEG_CHUNK_MAX = 128;           // ... K at least 1 and at most this
+inline uint32_t degrees_chunk(uint64_t n, uint32_t E) {
+  const uint64_t k = DEG_CHUNK_FELTS / (n * E);
+  return k < 1 ? 1u : k > DEG_CHUNK_MAX ? DEG_CHUNK_MAX : (uint32_t)k;
+}
+void launch_program_columns(Prof& prof, hipStream_t s, const ProgCode& code, const felt* ext, uint32_t width,
+                            uint32_t logn, uint32_t logE, uint32_t i0, uint32_t K, felt* out);
+// deg[k] (signed, preset to -1) = the highest index of a non-zero coefficient of column k < K
+// (k_column_degrees). Column k is E segments of n at coefs + k*E*n in the library's
+// bit-reversed, n-scaled layout: position p of segment m holds coefficient m*n + rev(p).
+void launch_column_degrees(Prof& prof, hipStream_t s, const felt* coefs, uint32_t logn, uint32_t logE, uint32_t K,
+                           long long* deg);
+
 // GlobalUpdate column pairing (kernels.hip): columns d+i from columns i < d for a
 // trace whose transitions hold. check: rows [t0, t0 + 2^logtn) of pairs c0..c0+cw of
 // the natural trace (*bad = 1 on a mismatch; row 0 gives c_i); coef: the derived
@@ -437,7 +457,8 @@ void launch_gu_fill(Prof& prof, hipStream_t s, felt* lde, uint32_t w, uint32_t l
 
 // composition polynomial from CE-coset interpolations (see kernels.hip): for the
 // bit-reversed positions [p0, p0 + nR), n * c_m = (sum_u Si_u * W_u * w_ce^-um) * g^-mn / ce;
-// consts = [g^-mn / ce for m < C | w_ce^-k for k < ce/2] (ce in {2, 4, 8, 16})
+// consts = [g^-mn / ce for m < C | w_ce^-k for k < ce/2] (ce in {2, 4, 8, 16}; 32 for
+// zkp_air_constraint_degrees_device, which keeps all C = ce segments)
 void launch_comp_dft(Prof& prof, hipStream_t s, const felt* recv, const uint32_t* blk, const felt* Si,
                      const felt* consts, uint32_t ce, uint32_t C, uint32_t logn, uint64_t p0, uint64_t nR, felt* out,
                      uint32_t* hi_flag = nullptr);
